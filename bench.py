@@ -82,7 +82,13 @@ def parse(argv=None):
     ap.add_argument("--score-streams", type=int, default=0,
                     help="side streams over which the scoring calls of consecutive layers are issued (0 = the library's choice: three with "
                          "the pruned call, two otherwise; 1 = caller's stream)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float32 / float64, at most 64 MB: "
+                         "a fixed seeded sample of the scores, the mask and the pruned cache; see dump_outputs), so that two builds "
+                         "can be compared output for output (e.g. --dump-outputs bench_outputs/)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.ratio is None:
         args.ratio = 0.6 if args.level == "head" else 0.3
     return args
@@ -374,6 +380,56 @@ def parity_violations(name, d, want=None, got=None, v_ref=None, v_got=None, thre
     return out
 
 
+DUMP_LIMIT_BYTES = 64_000_000   # everything --dump-outputs writes, headers included
+
+
+def dump_outputs(out_dir, records, score, valid, key_cache, value_cache, seg_start, len_k_host, seed=0):
+    """``--dump-outputs``: what the last timed step handed its caller, as ``out_dir/<name>.npy``:
+        threshold, real_ratio  [contexts]            float64  what prune() returned, per context (the gathered records of every rank)
+        len_k                  [contexts, L, Hkv]    float64  rows of each (layer, head) in the pruned cache
+        score, valid           [n]                   float32  scores and eviction mask ([L, 1, Hkv, N]) at n fixed flat positions
+        key, value             [L, r, D]             float32  r rows of each layer of the pruned cache, at fixed positions among its
+                                                              rows (which head and which row follows from len_k)
+    The per-token outputs are far larger than DUMP_LIMIT_BYTES at the headline size, so they are sampled: the positions are drawn
+    from a generator seeded with ``seed`` and depend on nothing but the shapes (and, for key / value, on len_k)."""
+    import numpy as np
+    g = torch.Generator().manual_seed(seed)
+    per_array = (DUMP_LIMIT_BYTES - (1 << 20)) // 4    # score, valid, key, value; 1 MiB for the small arrays and the headers
+    out = {
+        "threshold": np.array([r["thres"] for r in records], np.float64),
+        "real_ratio": np.array([r["real_ratio"] for r in records], np.float64),
+        "len_k": np.stack([r["len_k"].numpy() for r in records]).astype(np.float64),
+    }
+    n, n_max = score.numel(), per_array // 4
+    idx = torch.arange(n) if n <= n_max else torch.sort(torch.randint(0, n, (n_max,), generator=g)).values
+    idx = idx.to(score.device)
+    out["score"] = score.reshape(-1)[idx].float().cpu().numpy()
+    out["valid"] = valid.reshape(-1)[idx].float().cpu().numpy()
+    L, D = len(key_cache), key_cache[0].shape[-1]
+    u = torch.sort(torch.rand(max(1, per_array // (4 * L * D)), generator=g, dtype=torch.float64)).values
+    for name, cache in (("key", key_cache), ("value", value_cache)):
+        rows_out = []
+        for l in range(L):
+            lens = torch.tensor(len_k_host[l], dtype=torch.int64)
+            ends = torch.cumsum(lens, 0)
+            total = int(ends[-1])
+            if total == 0:
+                rows_out.append(torch.full((u.numel(), D), float("nan")))
+                continue
+            pos = (u * total).long().clamp_max(total - 1)                  # positions among the layer's rows, head after head
+            h = torch.searchsorted(ends, pos, right=True)
+            rows = seg_start[l].cpu().long()[h] + pos - (ends - lens)[h]
+            rows_out.append(cache[l].index_select(0, rows.to(cache[l].device)).float().cpu())
+        out[name] = torch.stack(rows_out).numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in out.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    written = sum(os.path.getsize(os.path.join(out_dir, name + ".npy")) for name in out)
+    assert written <= DUMP_LIMIT_BYTES, written
+    return sorted(out)
+
+
 def _run(args):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local_rank)
@@ -511,6 +567,9 @@ def _run(args):
     elapsed = ranks.max_over_ranks(time.perf_counter() - t0, dev)
     timing["on"] = False
     assert len(records) == world and all(r is not None and r["n_kept"] > 0 for r in records)
+    if args.dump_outputs and rank == 0:   # (the last step's cache, before the decode below appends to it)
+        dump_outputs(args.dump_outputs, records, kv._stacked_score(kv.score), kv.valid, kv.key_cache, kv.value_cache,
+                     kv.info["seg_start"], kv.info["len_k_host"])
 
     prof = {n: prof_read(lib, n) for n in ("score_rowstat", "score_bounds", "score_colmax", "select", "select_heads", "compact_gather")}
 

@@ -31,7 +31,7 @@ ranks.barrier(torch.cuda.synchronize)
 out = {"thres": recs[0]["thres"], "ratio": recs[0]["real_ratio"], "n_kept": recs[0]["n_kept"], "n": len(recs),
        "len_ok": bool(torch.equal(recs[0]["len_k"], len_k.cpu())), "t": t, "version": backend_version()}
 ranks.close()
-print("RCCL " + json.dumps(out))
+print("KVZ_RCCL_RESULT " + json.dumps(out))   # (RCCL prints its own "RCCL version : ..." banner on stdout)
 """
 
 
@@ -39,9 +39,9 @@ print("RCCL " + json.dumps(out))
 def test_rccl_single_rank_gather_and_max():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     p = subprocess.run([sys.executable, "-c", CHILD, ROOT], env=env, capture_output=True, text=True, timeout=600)
-    line = [l for l in p.stdout.splitlines() if l.startswith("RCCL ")]
+    line = [l for l in p.stdout.splitlines() if l.startswith("KVZ_RCCL_RESULT ")]
     assert p.returncode == 0 and line, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
-    d = json.loads(line[0][5:])
+    d = json.loads(line[0][len("KVZ_RCCL_RESULT "):])
     print("RCCL on this box:", d["version"])
     assert d["n"] == 1 and d["thres"] == 0.1259765625 and d["ratio"] == 0.2998 and d["len_ok"] and d["t"] == 0.75
     assert d["n_kept"] == sum(1000 * i + 7 for i in range(28 * 4))

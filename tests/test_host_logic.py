@@ -295,3 +295,59 @@ def test_bench_parity_gate_uses_the_test_suite_bounds():
     assert len(bench.parity_violations("f16", d, want, got, v_ref, v_got, 0.5)) == 1      # identical score, flipped entry: never
     d[j] = 1
     assert bench.parity_violations("f16", d, want, got, v_ref, v_got, float(want[j - 1])) == []
+
+
+def test_bench_dump_outputs_sample_is_bounded_reproducible_and_inside_the_pruned_rows(tmp_path):
+    """bench.py --dump-outputs at the headline geometry (Qwen2.5-7B: L28 Hkv4 D128, N = 131 072): float32 / float64 files of at most
+    64 MB in all, the same bytes from the same outputs, scores and mask sampled at the same positions, and every dumped cache row one of
+    the rows of its layer's head segments (never a slack row); a small output is written whole."""
+    import os
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    L, Hkv, N, D, slack = 28, 4, 131072, 128, 16
+    g = torch.Generator().manual_seed(3)
+    score = torch.rand(L, 1, Hkv, N, generator=g).half()
+    valid = score > 0.7
+    len_k = torch.randint(1, 40, (L, Hkv), generator=g, dtype=torch.int32)
+    len_k[3, 1] = 0                                                        # an empty head inside a layer
+    seg_start, key_cache, value_cache = [], [], []
+    for l in range(L):
+        starts = (torch.cumsum(len_k[l] + slack, 0) - len_k[l] - slack).to(torch.int32)
+        seg_start.append(starts)
+        rows = torch.full((int(starts[-1] + len_k[l, -1] + slack), D), -1.0)   # slack rows: -1
+        for h in range(Hkv):
+            a, n = int(starts[h]), int(len_k[l, h])
+            rows[a:a + n] = torch.arange(a, a + n, dtype=torch.float32).unsqueeze(1) + 1000.0 * l
+        key_cache.append(rows)
+        value_cache.append(-rows)
+    records = [{"thres": 0.25, "real_ratio": 0.3, "len_k": len_k}, {"thres": 0.5, "real_ratio": 0.31, "len_k": len_k + 1}]
+    args = (records, score, valid, key_cache, value_cache, seg_start, len_k.tolist())
+    names = bench.dump_outputs(str(tmp_path / "a"), *args)
+    bench.dump_outputs(str(tmp_path / "b"), *args)
+    assert names == ["key", "len_k", "real_ratio", "score", "threshold", "valid", "value"]
+    out = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in names) <= 64_000_000 == bench.DUMP_LIMIT_BYTES
+    assert all((tmp_path / "a" / f"{n}.npy").read_bytes() == (tmp_path / "b" / f"{n}.npy").read_bytes() for n in names)
+    assert out["threshold"].tolist() == [0.25, 0.5] and out["real_ratio"].tolist() == [0.3, 0.31]
+    assert np.array_equal(out["len_k"], np.stack([len_k.numpy(), len_k.numpy() + 1]).astype(np.float64))
+    # scores and mask: the same positions, and the mask is the one of those scores
+    assert out["score"].shape == out["valid"].shape and 1 << 20 < out["score"].size < score.numel()
+    assert np.array_equal(out["valid"], (out["score"] > np.float32(np.float16(0.7))).astype(np.float32))
+    # cache rows: each one inside a head segment of its layer, K and V the same rows, rows spread over the whole layer
+    k, v = out["key"], out["value"]
+    assert k.shape[0] == L and k.shape[2] == D and np.array_equal(v, -k) and (k == k[:, :, :1]).all()
+    for l in range(L):
+        idx = k[l, :, 0] - 1000.0 * l
+        inside = np.zeros(idx.shape, bool)
+        for h in range(Hkv):
+            a, n = int(seg_start[l][h]), int(len_k[l, h])
+            inside |= (idx >= a) & (idx < a + n)
+        assert inside.all(), l
+        assert len(np.unique(idx)) == int(len_k[l].sum()), l                # r >> rows in use: every row is drawn
+    # a small output is dumped whole
+    small = bench.dump_outputs(str(tmp_path / "c"), records[:1], score[:2, :, :, :64], valid[:2, :, :, :64], key_cache[:2],
+                               value_cache[:2], seg_start[:2], len_k[:2].tolist())
+    assert np.array_equal(np.load(tmp_path / "c" / "score.npy"), score[:2, :, :, :64].float().reshape(-1).numpy()) and "key" in small
