@@ -1059,3 +1059,85 @@ def test_varlen_attn_vs_an_independent_flash_implementation(dtype):
                     pad = torch.zeros(1, G, lens[h] - q_len, D, dtype=dtype, device=DEV)
                     want = F.scaled_dot_product_attention(torch.cat([pad, qh], dim=2), kh, vh, is_causal=True)[:, :, -q_len:]
             check_attn(f"vs_torch_flash/{dtype}/q{q_len}/h{h}", got[h].permute(1, 0, 2), want[0], tol, ulp_of=dtype)
+
+
+# ------------------------------------------------------------------------------------------------
+# a4 selection across its launch geometry (sel_blocks x emit_blocks)
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows,row_len", [(1, 13), (1, 4099), (224, 1000), (224, 4099), (384, 4096), (384, 13), (1000, 4096),
+                                          (1000, 4099)])
+def test_select_threshold_over_launch_geometries(rows, row_len):
+    """The selection grids are sized from sel_blocks and emit_blocks (default: one block per CU); every split of the scores over
+    blocks - one block, a few, more blocks than rows, more than CUs - gives the oracle's mask, threshold, kept count and row counts
+    bit for bit, on the plain path and on the prehist path (first histogram from kvz_score_finalize_log_hist).  384 rows = 48
+    layers x 8 heads: more rows than CUs; row_len % 8 != 0 takes the scalar path."""
+    o = ops()
+    lib = o._lib.load()
+    dtype = torch.float16 if (rows + row_len) % 2 else torch.bfloat16
+    n = rows * row_len
+    g = torch.Generator().manual_seed(n)
+    logs = -(torch.rand(n, generator=g) * 9.0)
+    logs[::13] = 0.0
+    log_bits = logs.view(torch.int32).clone()
+    log_bits[logs == 0.0] = 1                                         # (pass B's encoding of a value >= 0)
+    log_d = log_bits.to(DEV)
+    score = torch.empty(n, dtype=dtype, device=DEV)
+    st = o._stream(score)
+    o.check(lib.kvz_score_finalize_log(log_d.data_ptr(), n, score.data_ptr(), o._dtype_code(dtype), st), "finalize")
+    score = score.view(rows, 1, 1, row_len)
+    ws = o.select_workspace(DEV)
+    hist_dst = torch.empty_like(score)
+    ratios = (0.0, 0.05, 0.3, 0.97)
+    wants = {r: orc.threshold(score.cpu(), r) for r in ratios}
+    fails = []
+    for sb in (1, 2, 3, 7, 0, 1024):
+        for eb in (1, 5, 0, 4096):
+            prev_s = lib.kvz_debug_set_tunable(b"sel_blocks", sb)
+            prev_e = lib.kvz_debug_set_tunable(b"emit_blocks", eb)
+            try:
+                for ratio in ratios:
+                    want_v, want_t = wants[ratio]
+                    want_rows = want_v.view(-1, row_len).sum(-1).int()
+                    for pre in (False, True):
+                        if pre:
+                            o.check(lib.kvz_score_finalize_log_hist(log_d.data_ptr(), n, hist_dst.data_ptr(), o._dtype_code(dtype),
+                                                                    ws.data_ptr(), ws.numel(), st), "finalize_hist")
+                            assert torch.equal(hist_dst.view(torch.int16), score.view(torch.int16))
+                        v, t, k, rc = o.select_threshold(hist_dst if pre else score, ratio, row_len=row_len, prehist=ws if pre else None)
+                        if not (torch.equal(v.cpu(), want_v) and float(t.item()) == want_t and int(k.item()) == int(want_v.sum())
+                                and torch.equal(rc.cpu(), want_rows)):
+                            fails.append((sb, eb, ratio, pre))
+            finally:
+                lib.kvz_debug_set_tunable(b"sel_blocks", prev_s)
+                lib.kvz_debug_set_tunable(b"emit_blocks", prev_e)
+    assert not fails, fails[:16]
+
+
+# ------------------------------------------------------------------------------------------------
+# a10 dense append (pre-prune cache)
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype,D", [(torch.float16, 128), (torch.bfloat16, 64)])
+@pytest.mark.parametrize("t", [1, 13, 2026])
+def test_dense_append_bit_exact(dtype, D, t):
+    """kvz_dense_append against a torch slice copy: state views that are not contiguous (the [1, t, Hkv, D] -> [1, Hkv, t, D] transpose
+    a model hands over, and a row window of a longer tensor), fill not a multiple of 8, sentinel rows beyond fill + t untouched."""
+    o = ops()
+    lib = o._lib.load()
+    Hkv = 3
+    g = torch.Generator(device=DEV).manual_seed(t + D)
+    for fill in (0, 5, 13):
+        cap = fill + t + 7
+        cache_k = torch.randn(1, Hkv, cap, D, generator=g, device=DEV).to(dtype)
+        cache_v = torch.randn(1, Hkv, cap, D, generator=g, device=DEV).to(dtype)
+        ks = torch.randn(1, t, Hkv, D, generator=g, device=DEV).to(dtype).transpose(1, 2)            # row stride Hkv * D
+        vs = torch.randn(1, Hkv, t + 3, D, generator=g, device=DEV).to(dtype)[:, :, 2:2 + t]        # head stride (t + 3) * D, offset
+        assert (t == 1 or not ks.is_contiguous()) and not vs.is_contiguous()   # (a size-1 dim makes the transpose contiguous)
+        want_k, want_v = cache_k.clone(), cache_v.clone()
+        want_k[:, :, fill:fill + t] = ks
+        want_v[:, :, fill:fill + t] = vs
+        rc = lib.kvz_dense_append(cache_k.data_ptr(), cache_v.data_ptr(), cache_k.stride(1), fill, ks.data_ptr(), vs.data_ptr(),
+                                  ks.stride(1), ks.stride(2), vs.stride(1), vs.stride(2), Hkv, t, D, cache_k.element_size(),
+                                  o._stream(cache_k))
+        o.check(rc, "kvz_dense_append")
+        assert torch.equal(cache_k.view(torch.int16), want_k.view(torch.int16)), (fill, "K")
+        assert torch.equal(cache_v.view(torch.int16), want_v.view(torch.int16)), (fill, "V")
