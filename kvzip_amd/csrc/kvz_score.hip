@@ -780,7 +780,9 @@ __global__ __launch_bounds__(PA_WAVES * 64, PA_WAVES / 4) void score_rowstat2_ke
                 // it.  A lane whose 16 logits are all masked keeps its state (tmax = -inf).
                 if (tmax > m_ref[g] || (l_run[g] == 0.f && tmax > -INFINITY)) {
                     const float nml2_new = -(tmax * L2E);
-                    l_run[g] *= __builtin_amdgcn_exp2f(nml2_new - nml2_ref[g]);
+                    // (an empty sum stays 0: moving the reference DOWN by more than 128 in the exp2 domain makes the factor +inf, and
+                    // 0 * inf would poison the row - and through pass B its whole KV head - with NaN)
+                    l_run[g] = (l_run[g] == 0.f) ? 0.f : l_run[g] * __builtin_amdgcn_exp2f(nml2_new - nml2_ref[g]);
                     m_ref[g] = tmax;
                     nml2_ref[g] = nml2_new;
                 }
