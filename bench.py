@@ -7,11 +7,16 @@ One "step" = one full pass of the eviction hot path over one synthetic context t
         -> global-threshold selection (score.py:88-102) -> compaction of all layers (kvcache.py:152-185)
     --level head (BASELINE config C5, context-independent eviction, model/wrapper.py:40-58):
         head scores [L,Hkv] (the reference's utils/head_score values) -> head-level selection -> compaction of all layers
-driven through the drop-in cache object (kvzip_amd.EvictCache), followed (untimed for `value`) by post-prune decode steps.
+driven through the drop-in cache object (kvzip_amd.EvictCache).
 Weak scaling: every rank (one per GPU) owns one independent context; there is no data-path collective, only the gather of
 the per-context result record (kvzip_amd.dist.gather_results) inside the timed region.
 
-    python bench.py [--gpus N --steps K --warmup W]          # N > 1 without a launcher: spawns one process per GPU itself
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints its line; the kernel figures of `roofline` and
+`roofline_stages` come from hipEvent brackets inside the timed steps.  --full adds what takes runs of its own after the timed steps:
+post-prune decode steps, decode attention on a ragged layer, the box's HBM copy rates, and (one GPU) the CPU baseline with its
+parity sample against the oracle.
+
+    python bench.py [--gpus N --steps K --warmup W] [--full]  # N > 1 without a launcher: spawns one process per GPU itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.
@@ -61,9 +66,13 @@ def parse(argv=None):
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16"])
     ap.add_argument("--chunk", type=int, default=2000)       # model/wrapper.py:200
     ap.add_argument("--sink", type=int, default=32)
-    ap.add_argument("--decode-tokens", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--decode-unfused", action="store_true", help="decode with update / prepare / attend as three calls")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure post-prune decode (layer loop and HIP graph), decode attention on a ragged "
+                         "layer and the box's HBM copy rates, and on one GPU the CPU baseline with its parity sample against the oracle "
+                         "(exit code 3 when the sample violates the bounds)")
+    ap.add_argument("--decode-tokens", type=int, default=32, help="with --full: timed post-prune decode tokens")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and its parity sample")
+    ap.add_argument("--decode-unfused", action="store_true", help="with --full: decode with update / prepare / attend as three calls")
     ap.add_argument("--q-pool", type=int, default=0, help="distinct chunk inputs kept in HBM (0 = all chunks)")
     ap.add_argument("--inputs", default="gauss", choices=["gauss", "copy"],
                     help="gauss (default, the headline): independent Gaussian q / k; copy: repeat-prompt-like - the query (and the re-read key) of position i of "
@@ -567,94 +576,95 @@ def _run(args):
     elapsed = ranks.max_over_ranks(time.perf_counter() - t0, dev)
     timing["on"] = False
     assert len(records) == world and all(r is not None and r["n_kept"] > 0 for r in records)
-    if args.dump_outputs and rank == 0:   # (the last step's cache, before the decode below appends to it)
+    if args.dump_outputs and rank == 0:   # (the last step's cache, before --full's decode appends to it)
         dump_outputs(args.dump_outputs, records, kv._stacked_score(kv.score), kv.valid, kv.key_cache, kv.value_cache,
                      kv.info["seg_start"], kv.info["len_k_host"])
 
     prof = {n: prof_read(lib, n) for n in ("score_rowstat", "score_bounds", "score_colmax", "select", "select_heads", "compact_gather")}
 
-    # ---- post-prune decode: append + variable-length attention, q_len = 1 (attention only) ------------------
-    lib.kvz_prof_reset()
-    T = args.decode_tokens
-    qd = randn(L, 1, H, 1, D)
-    kd, vd = randn(L, 1, Hkv, 1, D), randn(L, 1, Hkv, 1, D)
-
-    def decode_tokens(n):
-        for _ in range(n):
-            for l in range(L):
-                if args.decode_unfused:
-                    kf, vf = kv.update(kd[l], vd[l], l)
-                    qf, kf, vf, info = kv.prepare(qd[l], kf, vf, l)
-                    kv.attend(qf, kf, vf, info)
-                else:  # what kvzip_amd/attn.py does for a generation step: append + attention in one launch
-                    kv.update_attend(qd[l], kd[l], vd[l], l)
-    seen = kv._seen_tokens
-    decode_tokens(2)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    decode_tokens(T)
-    torch.cuda.synchronize()
-    t_dec = time.perf_counter() - t0
-    # kernel durations: a few more tokens with the library's hipEvent brackets (kept out of the timed loop: two event records per
-    # launch are host work)
-    lib.kvz_prof_reset()
-    lib.kvz_prof_enable(1)
-    decode_tokens(min(T, 4))
-    torch.cuda.synchronize()
-    lib.kvz_prof_enable(0)
-    # the same step as ONE HIP graph (EvictCache.decode_graph: static input buffers, device-side token counter): what a serving
-    # engine replays per token; the per-layer loop above is what a Python forward pass does
-    t_graph = None
-    if T > 0 and not args.decode_unfused:
-        step_graph = kv.decode_graph(qd, kd, vd)
-        for _ in range(2):
-            step_graph.replay()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(T):
-            step_graph.replay()
-        torch.cuda.synchronize()
-        t_graph = time.perf_counter() - t0
-    attn_ms, attn_n = prof_read(lib, "varlen_attn")
     kept_rows = sum(kv.info["rows_used"])
     len_k_host = kv.info["len_k_host"]
-    kv.slice(seen)
+    T = args.decode_tokens
+    t_dec = t_graph = ragged = copy_gbs = copyk = None
+    attn_ms, attn_n = 0.0, 0
+    if args.full:
+        # ---- post-prune decode: append + variable-length attention, q_len = 1 (attention only) ------------------
+        lib.kvz_prof_reset()
+        qd = randn(L, 1, H, 1, D)
+        kd, vd = randn(L, 1, Hkv, 1, D), randn(L, 1, Hkv, 1, D)
 
-    # ---- the same attention call on an AdaKV-style RAGGED layer (head lengths 39 k / 4 k / 120 k / 500 ...): work items are cut
-    # from the sum of the lengths, so the GPU fills the same way --------------------------------
-    ragged = None
-    if rank == 0 and T > 0:
-        base = [39000, 4000, 120000, 500]
-        lens_r = [base[h % 4] for h in range(Hkv)]
-        starts_r, acc = [], 0
-        for n_ in lens_r:
-            starts_r.append(acc)
-            acc += n_ + 1024
-        kr_, vr_ = randn(acc, D), randn(acc, D)
-        qr_ = randn(Hkv, H // Hkv, D)
-        ks_ = torch.tensor(starts_r, dtype=torch.int32, device=dev)
-        kl_ = torch.tensor(lens_r, dtype=torch.int32, device=dev)
-        ws_ = ops.attn_workspace(Hkv, H // Hkv, 1, D, dev)
-        meta_ = ops._meta_host(starts_r, lens_r, Hkv)
-        for _ in range(3):
-            ops.varlen_attn(qr_, kr_, vr_, ks_, kl_, 1, max(lens_r), workspace=ws_, meta_host=meta_)
+        def decode_tokens(n):
+            for _ in range(n):
+                for l in range(L):
+                    if args.decode_unfused:
+                        kf, vf = kv.update(kd[l], vd[l], l)
+                        qf, kf, vf, info = kv.prepare(qd[l], kf, vf, l)
+                        kv.attend(qf, kf, vf, info)
+                    else:  # what kvzip_amd/attn.py does for a generation step: append + attention in one launch
+                        kv.update_attend(qd[l], kd[l], vd[l], l)
+        seen = kv._seen_tokens
+        decode_tokens(2)
         torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        decode_tokens(T)
+        torch.cuda.synchronize()
+        t_dec = time.perf_counter() - t0
+        # kernel durations: a few more tokens with the library's hipEvent brackets (kept out of the timed loop: two event records per
+        # launch are host work)
         lib.kvz_prof_reset()
         lib.kvz_prof_enable(1)
-        for _ in range(50):
-            ops.varlen_attn(qr_, kr_, vr_, ks_, kl_, 1, max(lens_r), workspace=ws_, meta_host=meta_)
+        decode_tokens(min(T, 4))
         torch.cuda.synchronize()
         lib.kvz_prof_enable(0)
-        r_ms, r_n = prof_read(lib, "varlen_attn")
-        r_bytes = 2.0 * sum(lens_r) * D * 2
-        if r_n:
-            ragged = {"bound": "hbm", "achieved": r_bytes / (r_ms / r_n / 1e3) / 1e9, "unit": "GB/s",
-                      "frac": r_bytes / (r_ms / r_n / 1e3) / 1e9 / HBM_PEAK_GBS, "avg_ms": r_ms / r_n, "launches": r_n,
-                      "algorithmic_bytes": r_bytes, "head_lengths": lens_r}
-        del kr_, vr_
+        # the same step as ONE HIP graph (EvictCache.decode_graph: static input buffers, device-side token counter): what a serving
+        # engine replays per token; the per-layer loop above is what a Python forward pass does
+        if T > 0 and not args.decode_unfused:
+            step_graph = kv.decode_graph(qd, kd, vd)
+            for _ in range(2):
+                step_graph.replay()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(T):
+                step_graph.replay()
+            torch.cuda.synchronize()
+            t_graph = time.perf_counter() - t0
+        attn_ms, attn_n = prof_read(lib, "varlen_attn")
+        kv.slice(seen)
 
-    copy_gbs = hbm_copy_ceiling(dev) if rank == 0 else None
-    copyk = hbm_copy_kernel_ceiling(lib, dev) if rank == 0 else None
+        # ---- the same attention call on an AdaKV-style RAGGED layer (head lengths 39 k / 4 k / 120 k / 500 ...): work items are cut
+        # from the sum of the lengths, so the GPU fills the same way --------------------------------
+        if rank == 0 and T > 0:
+            base = [39000, 4000, 120000, 500]
+            lens_r = [base[h % 4] for h in range(Hkv)]
+            starts_r, acc = [], 0
+            for n_ in lens_r:
+                starts_r.append(acc)
+                acc += n_ + 1024
+            kr_, vr_ = randn(acc, D), randn(acc, D)
+            qr_ = randn(Hkv, H // Hkv, D)
+            ks_ = torch.tensor(starts_r, dtype=torch.int32, device=dev)
+            kl_ = torch.tensor(lens_r, dtype=torch.int32, device=dev)
+            ws_ = ops.attn_workspace(Hkv, H // Hkv, 1, D, dev)
+            meta_ = ops._meta_host(starts_r, lens_r, Hkv)
+            for _ in range(3):
+                ops.varlen_attn(qr_, kr_, vr_, ks_, kl_, 1, max(lens_r), workspace=ws_, meta_host=meta_)
+            torch.cuda.synchronize()
+            lib.kvz_prof_reset()
+            lib.kvz_prof_enable(1)
+            for _ in range(50):
+                ops.varlen_attn(qr_, kr_, vr_, ks_, kl_, 1, max(lens_r), workspace=ws_, meta_host=meta_)
+            torch.cuda.synchronize()
+            lib.kvz_prof_enable(0)
+            r_ms, r_n = prof_read(lib, "varlen_attn")
+            r_bytes = 2.0 * sum(lens_r) * D * 2
+            if r_n:
+                ragged = {"bound": "hbm", "achieved": r_bytes / (r_ms / r_n / 1e3) / 1e9, "unit": "GB/s",
+                          "frac": r_bytes / (r_ms / r_n / 1e3) / 1e9 / HBM_PEAK_GBS, "avg_ms": r_ms / r_n, "launches": r_n,
+                          "algorithmic_bytes": r_bytes, "head_lengths": lens_r}
+            del kr_, vr_
+
+        copy_gbs = hbm_copy_ceiling(dev) if rank == 0 else None
+        copyk = hbm_copy_kernel_ceiling(lib, dev) if rank == 0 else None
     copyk_gbs = max(copyk.values()) if copyk else None
     # every rank's own time for the timed steps (N = 1-comparable: a SCALE line can be checked against the BENCH line per rank)
     per_rank_ms = [own_elapsed / args.steps * 1e3]
@@ -702,17 +712,18 @@ def _run(args):
                            # ... and against a plain 16-bytes-per-lane copy KERNEL on this box (the guide's yardstick for achievable HBM bandwidth)
                            "hbm_copy_kernel_GBps_this_box": copyk,
                            "frac_of_box_copy_kernel": (c_gbs / copyk_gbs) if (c_gbs and copyk_gbs) else None},
-        "decode_varlen_attn": {"bound": "hbm", "achieved": attn_gbs, "unit": "GB/s",
-                               "frac": (attn_gbs / HBM_PEAK_GBS) if attn_gbs else None,
-                               "avg_ms": (attn_ms / attn_n) if attn_n else None, "launches": attn_n,
-                               "algorithmic_bytes": decode_bytes / L,
-                               "traffic": pmc.get("varlen_attn_split", {}).get("traffic_bytes"),
-                               # the same stage from the un-bracketed token loop (two hipEvent records per launch pair cost ~3 us)
-                               "loop_us_per_layer": (t_dec / T / L * 1e6) if T else None,
-                               "frac_loop": (decode_bytes / L / (t_dec / T / L) / 1e9 / HBM_PEAK_GBS) if T else None},
     }
-    if ragged is not None:
-        stages["decode_varlen_attn_ragged"] = ragged
+    if args.full:
+        stages["decode_varlen_attn"] = {"bound": "hbm", "achieved": attn_gbs, "unit": "GB/s",
+                                        "frac": (attn_gbs / HBM_PEAK_GBS) if attn_gbs else None,
+                                        "avg_ms": (attn_ms / attn_n) if attn_n else None, "launches": attn_n,
+                                        "algorithmic_bytes": decode_bytes / L,
+                                        "traffic": pmc.get("varlen_attn_split", {}).get("traffic_bytes"),
+                                        # the same stage from the un-bracketed token loop (two hipEvent records per launch pair cost ~3 us)
+                                        "loop_us_per_layer": (t_dec / T / L * 1e6) if T else None,
+                                        "frac_loop": (decode_bytes / L / (t_dec / T / L) / 1e9 / HBM_PEAK_GBS) if T else None}
+        if ragged is not None:
+            stages["decode_varlen_attn_ragged"] = ragged
     if head_level:
         h_ms, h_n = prof["select_heads"]
         stages["select_heads"] = {"bound": "launch", "avg_ms": h_ms / h_n if h_n else None, "launches": h_n,
@@ -849,6 +860,7 @@ def _run(args):
                                                                         # per call instead of three); the bracketed calls of roofline_stages run the chained form (3)
             "hbm_copy_GBps_this_box": copy_gbs,   # 1-GiB device-to-device copy (read + write), same process: the box's own HBM ceiling
             "tune": args.tune,
+            "full": args.full,
         },
         "roofline": roofline,
         "roofline_stages": stages,
@@ -856,9 +868,9 @@ def _run(args):
                    "ms_per_token_hip_graph": (t_graph / T * 1e3) if t_graph else None,
                    "what": "per token: L x (O(1) append of K,V + variable-length attention), model MLP/projections excluded; "
                            "ms_per_token = the step issued layer by layer from Python (kv.update_attend, what kvzip_amd.attn does), "
-                           "ms_per_token_hip_graph = the same step replayed as one HIP graph (EvictCache.decode_graph)"},
+                           "ms_per_token_hip_graph = the same step replayed as one HIP graph (EvictCache.decode_graph)"} if args.full else None,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], parity = cpu_baseline(args, L, H, Hkv, D, dtype, dev, head_scores)
         if parity is not None:
             out["parity_sample"] = parity

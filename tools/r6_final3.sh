@@ -6,5 +6,5 @@ python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" 2>&1 | tai
 timeout 900 python tools/fuzz_tail.py 60 2 > $O/fuzz_tail.txt 2>&1; tail -1 $O/fuzz_tail.txt
 bash tools/final_profile_r6b.sh prof 2>&1 | tail -30
 bash tools/final_profile_r6b.sh bench 2>&1 | tail -13
-python bench.py --gpus 1 --steps 20 --warmup 5 --inputs copy > $O/bench_c4_copy_like.json 2> $O/bench_c4_copy_like.err; python -c "
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --inputs copy > $O/bench_c4_copy_like.json 2> $O/bench_c4_copy_like.err; python -c "
 import json; d=json.loads(open('$O/bench_c4_copy_like.json').read().strip().splitlines()[-1]); print('copy-like', round(d['value']), d.get('parity_ok'))"

@@ -3,7 +3,7 @@
 O=gpurun_out/r6full; mkdir -p $O
 timeout 3000 python -m pytest tests -q -m gpu -s 2>&1 | grep -E "PARITY|E2E|MASK|G15|UNIFORM|passed|failed|Error|error|scores equal" > $O/pytest_gpu.txt; tail -4 $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" 2>&1 | tail -1
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; python - <<'PY'
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r6full/bench_default.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], 'parity_ok', d.get('parity_ok'))
