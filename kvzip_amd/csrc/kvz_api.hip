@@ -101,18 +101,25 @@ static const char* const g_tune_name[TUNE_COUNT] = {"attn_items", "flash_min_row
 // sel_blocks / emit_blocks: 1024-thread blocks of the histogram passes / of the mask pass of the global-threshold selection (default 0 =
 //   one per CU, device_cus(): every block costs a histogram flush or a prologue, profiles/r4_select.txt).
 // NOTE: debug / measurement hooks - process-wide, set them while no other thread is launching (tests and tools/ only).
-// score_prune (both dtypes, deferred-log entry points, chunks of >= 32 query positions; everything else takes the two full passes whatever the knob says): 3 = key-per-lane
-//   row statistics + candidate keys per row group + gathered column maxima (kvz_score.hip, round 6: four launches); 6 (default) = the same kernels, the three small launches of
-//   the asynchronous calls as ONE launch pipelined over the calls of a side stream (score_tail_kernel; synchronous entry points and workspaces below three sets: 3);
-//   5 = candidate (group, key block) pairs (round 5); 0 = two full passes over
-//   Q.K^T; 1 / 4 = check variants (key-per-lane statistics with the full column-maximum pass / every (group, key) item through the candidate pass); 16 + mask: launches left out
-//   (time measurements only).  KVZIP_SCORE_PRUNE presets it.
+// score_prune (both dtypes, deferred-log entry points, chunks of >= 32 query positions; everything else takes the two full passes whatever
+//   the knob says; kvz_score.hip:launch_score_impl): 6 (default) = key-per-lane row statistics + candidate keys per row group + gathered
+//   column maxima, the three small launches of the asynchronous calls as ONE launch pipelined over the calls of a side stream
+//   (score_tail_kernel; synchronous entry points and workspaces below three sets: 3); 3 = the same kernels as four launches; 0 = two full
+//   passes over Q.K^T; 1 / 4 = check variants (key-per-lane statistics with the full column-maximum pass / every (group, key) item through
+//   the candidate pass).  No other value is accepted (score_prune_ok).  KVZIP_SCORE_PRUNE presets it.
 static const int g_tune_default[TUNE_COUNT] = {0, 64, 128, 1, 0, 0, 1, 6};   // (0 for attn_items / sel_blocks / emit_blocks: derived from device_cus())
 static std::atomic<int> g_tune[TUNE_COUNT] = {{0}, {64}, {128}, {1}, {0}, {0}, {1}, {6}};   // (atomic: a probe may flip a knob while another thread launches)
+// the values score_prune takes; negative values stand for the default
+static bool score_prune_ok(long v) { return v < 0 || v == 0 || v == 1 || v == 3 || v == 4 || v == 6; }
 // (KVZIP_SCORE_PRUNE in the environment presets the score_prune knob when the library is loaded: A/B runs of whole programs)
 static const int g_tune_env = [] {
     const char* e = getenv("KVZIP_SCORE_PRUNE");
-    if (e && *e) g_tune[TUNE_SCORE_PRUNE].store(atoi(e), std::memory_order_relaxed);
+    if (e && *e) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (*end || !score_prune_ok(v)) fprintf(stderr, "libkvzip_hip: KVZIP_SCORE_PRUNE=%s ignored (valid: 0, 1, 3, 4, 6)\n", e);
+        else if (v >= 0) g_tune[TUNE_SCORE_PRUNE].store((int)v, std::memory_order_relaxed);
+    }
     return 0;
 }();
 int tunable(Tunable t) { return g_tune[t].load(std::memory_order_relaxed); }
@@ -129,6 +136,8 @@ extern "C" int kvz_debug_set_tunable(const char* name, int value) {
     KVZ_REQUIRE(name, KVZ_EINVAL, "kvz_debug_set_tunable: null name");
     for (int i = 0; i < kvz::TUNE_COUNT; ++i)
         if (strcmp(name, kvz::g_tune_name[i]) == 0) {
+            KVZ_REQUIRE(i != kvz::TUNE_SCORE_PRUNE || kvz::score_prune_ok(value), KVZ_EINVAL,
+                        "kvz_debug_set_tunable: score_prune %d (valid: 0, 1, 3, 4, 6; negative: the default)", value);
             // (value <= 0 restores the default; the on / off knobs flash2_xcd, flash2_split and score_prune take 0 as "off" and negative
             // values as "default")
             const bool onoff = i == kvz::TUNE_FLASH2_XCD || i == kvz::TUNE_FLASH2_SPLIT || i == kvz::TUNE_SCORE_PRUNE;

@@ -60,16 +60,17 @@ struct ScoreArgs {
     FastDiv dq, dh;      // q_len, Hkv
     uint32_t* log_out;   // non-NULL: pass B merges its row slices by atomic unsigned-min on the bit patterns of the (non-positive)
     int64_t log_head_stride;  // fp32 log-scores into [Hkv, log_head_stride] instead of writing colpart; no finalize launch
-    // ---- exact pruning of pass B (round 5: score_rowstatT2_kernel, score_merge_kernel, score_bounds2_kernel, score_colmax_sparse_kernel)
+    // ---- exact pruning of pass B (score_rowstatT2_kernel, score_merge_kernel, score_bounds3_kernel, score_colmax_keys_kernel)
     uint16_t* colu;      // [Hkv, nkb, n_groups, 2, 32] (+ 128 spare bytes)  16-bit patterns of max over the 16 rows of each HALF of group g of the logit x_rj
     float2* gbound;      // [Hkv, n_groups]     (max, min) over the rows of group g of  n_r = -(m_r + log l_r);  (NaN, NaN): a row with NaN statistics
     float* nrow;         // [Hkv, 32 n_groups]  n_r per query row (-inf for the padding rows of the last group)
-    uint32_t* entries;   // [Hkv, nkb * n_groups] compacted candidate pairs per KV head: g | kb << 11 | h << 25, the pairs of one (h, kb) contiguous
-    uint32_t* counter;   // [Hkv] number of entries per head (zeroed by score_merge_kernel, filled by score_bounds2_kernel)
+    uint32_t* entries;   // [Hkv, nkb * n_groups] work queue per KV head of the candidate-key pass: g | k << 11 | h << 25 = chunk k (keys
+                         //   32 k .. 32 k + 31) of the candidate list of row group g, appended by score_bounds3_kernel, any order
+    uint32_t* counter;   // [Hkv] number of entries per head (zeroed by score_merge_kernel, filled by score_bounds3_kernel)
     uint32_t* redo;      // [PLAN_MAX_BLOCKS] per block of the key-per-lane pass: items to be redone by its slow loop (self-clearing)
     int n_groups, nkb;
-    int all_pairs;       // (debug knob: every pair is a candidate)
-    // ---- candidates at KEY granularity (round 6: score_bounds3_kernel, score_colmax_keys_kernel)
+    int all_pairs;       // (debug knob: every (group, key) pair is a candidate)
+    // ---- candidates at KEY granularity (score_bounds3_kernel, score_colmax_keys_kernel)
     uint32_t* gcount;    // [Hkv, n_groups]            candidate keys of row group g (zeroed by score_merge_kernel, filled by score_bounds3_kernel)
     uint32_t* klist;     // [Hkv, n_groups, kcap]      their ctx indices j (any order)
     int kcap;            // nkb * 32
@@ -195,9 +196,6 @@ __device__ static inline void stage_tile_linear(char* buf, const char* base, uin
 //    has been issued, not after its epilogue.  The tile stream runs across item boundaries.
 #ifndef KVZ_PA_FAR_BASE
 #define KVZ_PA_FAR_BASE 1
-#endif
-#ifndef KVZ_T2_BLOCKMASK
-#define KVZ_T2_BLOCKMASK 0
 #endif
 constexpr int PA_WAVES = 8;
 constexpr int PA_RG = 1;                        // 32-row groups per wave
@@ -1326,16 +1324,16 @@ __global__ __launch_bounds__(PB_WAVES * 64, PB_OCC) void score_colmax3_kernel(Sc
     }
 }
 
-// ---- pass A with one KEY per lane, exact pruning of pass B (round 5) ---------------------------------------------------------------------
+// ---- pass A with one KEY per lane, exact pruning of pass B -------------------------------------------------------------------------------
 // score_rowstatT2_kernel is score_rowstat2_kernel with the MFMA operands swapped: the 32 query rows of a wave are the A operand (registers),
 // key tiles stream through the LDS ring as the B operand, so a lane holds ONE key and its 16 accumulators are 16 query rows
 // (k -> row (k & 3) + 8 (k >> 2) + 4 half).  Row sums become 16 lane-partial accumulators, reduced across lanes once per item; what the layout
 // buys is the per-key maximum over the 32 rows of the wave - lane-local over the 16 registers plus one half swap - written as u[g][j] for
 // the ctx keys.  With n_r = -(m_r + log l_r):   max_{r in g} (x_rj + n_r) <= u_gj + max_g n   and   t_j >= max_g (u_gj + min_g n),
-// so the column maximum t_j only has to be recomputed for the (32-row group, 32-key block) pairs that bound cannot rule out - exactly (the
-// bounds use the fp32 addition the recomputation applies to a logit and a row's statistic, monotone in both arguments): 18 % of the pairs
-// on the benchmark's Gaussian logits, 3-21 % on copy-like prompts (tools/prune_bound_sim.py).  score_merge_kernel merges the partial
-// statistics into n_r and the group bounds, score_bounds2_kernel compacts the candidate pairs, score_colmax_sparse_kernel recomputes them.
+// so the column maximum t_j only has to be recomputed for the (32-row group, key) pairs that bound cannot rule out - exactly (the bounds
+// use the fp32 addition the recomputation applies to a logit and a row's statistic, monotone in both arguments): a key names two or three
+// of the 448 groups on the benchmark's inputs (tools/prune_bound_sim.py).  score_merge_kernel merges the partial statistics into n_r and
+// the group bounds, score_bounds3_kernel lists the candidate keys of every group, score_colmax_keys_kernel recomputes them.
 
 // first half of the rounding chain for four logits: x = half(float(half(acc)) * rcp) (FAST) or the division; packed results only
 // (round 6: v_fma_mixlo_f16 / v_fma_mixhi_f16 do the multiplication and the second rounding in one instruction per logit - six instead of
@@ -1944,56 +1942,18 @@ __global__ __launch_bounds__(PA_WAVES * 64, PA_WAVES / 4) void score_rowstatT2_k
         tile_ctx_full = __builtin_amdgcn_readfirstlane((k0 >= a.sink && k0 + SC_TILE <= a.sink + a.m) ? 1 : 0);
         const bool young = wave >= NWAVES / 2;
         auto nohook = [&]() __attribute__((always_inline)) {};
-        // a tile that holds a causal limit of the wave's rows (round 6): only the 32-key blocks that CUT the rows pay for the masks (the
-        // diagonal band of 32 rows touches one or two of the four); the blocks before it take the plain step, the blocks behind it are
-        // hidden from every row of the wave - and so is everything after them in this item: nothing to compute, nothing to prefetch (the
-        // next item opens with its own chain), only the hand-over in the third step
-        auto one = [&](f16v& accn, const f16v& accc, int kb0, auto s_tag, auto lb_tag, auto lkb_tag, auto&& hook) __attribute__((always_inline)) {
-            if constexpr (!decltype(mask_tag)::value) {
-                step(accn, accc, kb0, s_tag, std::false_type{}, lb_tag, lkb_tag, hook);
-            } else {
-#if KVZ_T2_BLOCKMASK >= 2
-                if (kb0 + 31 <= wmin) step(accn, accc, kb0, s_tag, std::false_type{}, lb_tag, lkb_tag, hook);
-                else
-#endif
-#if KVZ_T2_BLOCKMASK >= 1
-                if (kb0 <= wmax) {
-                    step(accn, accc, kb0, s_tag, std::true_type{}, lb_tag, lkb_tag, hook);
-                } else {
-                    // (the next block's chain and the fragment reads behind it are issued all the same - nothing will use them, but both
-                    // sides of the branch then define the same registers and the allocator has nothing to carry through the join)
-#pragma unroll
-                    for (int hg = 0; hg < 8; ++hg) {
-#pragma unroll
-                        for (int c = 0; c < MfmaSched<C::KK>::count(hg); ++c) {
-                            const int kk = MfmaSched<C::KK>::first(hg) + c;
-                            mfma_step(accn, kk);
-                            if (hg != 0) load_frag1(fr[kk], lb_tag, lkb_tag, kk);
-                        }
-                        if (hg == 0) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            hook();
-#pragma unroll
-                            for (int c = 0; c < MfmaSched<C::KK>::count(0); ++c) load_frag1(fr[MfmaSched<C::KK>::first(0) + c], lb_tag, lkb_tag, MfmaSched<C::KK>::first(0) + c);
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#else
-                step(accn, accc, kb0, s_tag, std::true_type{}, lb_tag, lkb_tag, hook);
-#endif
-            }
-        };
         if (young) __builtin_amdgcn_s_setprio(1);
-        one(acc[1], acc[0], k0, I0{}, b_tag, I2{}, nohook);
+        step(acc[1], acc[0], k0, I0{}, mask_tag, b_tag, I2{}, nohook);
         if (young) __builtin_amdgcn_s_setprio(0);
-        one(acc[0], acc[1], k0 + 32, I1{}, b_tag, I3{}, nohook);
+        step(acc[0], acc[1], k0 + 32, I1{}, mask_tag, b_tag, I3{}, nohook);
         if (young) __builtin_amdgcn_s_setprio(1);
-        one(acc[1], acc[0], k0 + 64, I2{}, IB1{}, I0{}, [&]() __attribute__((always_inline)) { turnover(b_tag); });
+        step(acc[1], acc[0], k0 + 64, I2{}, mask_tag, IB1{}, I0{}, [&]() __attribute__((always_inline)) { turnover(b_tag); });
         if (young) __builtin_amdgcn_s_setprio(0);
         // the chain issued here belongs to block 0 of the next tile; after the last tile of an item it is simply not used
-        one(acc[0], acc[1], k0 + 96, I3{}, IB1{}, I1{}, nohook);
+        step(acc[0], acc[1], k0 + 96, I3{}, mask_tag, IB1{}, I1{}, nohook);
     };
+    // a tile that holds a causal limit of the wave's rows takes the masked step in all four of its 32-key blocks (masking only the one or two
+    // blocks that cut the rows made the allocator spill and measured 1-3 % slower: EXPERIMENTS.md, round 6)
     auto tile_dispatch = [&](auto b_tag) __attribute__((always_inline)) {
         const bool masked = t * SC_TILE + SC_TILE - 1 > wmin;  // some key of the tile is hidden from some row of this wave
         if (masked) tile_steps(b_tag, std::true_type{});
@@ -2252,324 +2212,19 @@ __device__ static inline void score_merge_body(const ScoreArgs& a, const int uni
 }
 __global__ __launch_bounds__(PA_ROWS) void score_merge_kernel(ScoreArgs a) { score_merge_body(a, (int)blockIdx.x); }
 
-// ---- candidate pairs of pass B, compacted (round 5) -----------------------------------------------------------------------------------
-// One block per (KV head, 32-key block).  Its [n_groups][32] slab of u is contiguous (28 KiB at the headline shape): every thread reads 8
-// keys of one group per pass, all passes in flight at once.  LB_j = max_g (u_gj + nmin_g); group g is a candidate of the block iff
-// u_gj + nmax_g >= LB_j for some key j of the block (the fp32 addition pass B applies to a logit and its row's statistic: monotone in
-// both arguments, so the test is exact; NaN bounds keep the pair).  The candidates go into ONE list (entries), those of a block contiguous.
-// A head with a row of NaN statistics is poisoned as the reference's amax over rows poisons it: the block writes the NaN code itself.
+// ---- candidates at KEY granularity ---------------------------------------------------------------------------------------------------------
+// A (32-row group, 32-key block) pair recomputed in full - 1024 logits - would serve, typically, ONE key: every key has its argmax group (and
+// the one or two groups whose bound cannot rule them out), so a key block of 32 keys names ~55 of the 448 groups (18 % of the pairs on the
+// benchmark's inputs).  Turned around, a row group is named by ~31 KEYS of the whole chunk.  score_bounds3_kernel, one block per (KV head,
+// 32-key block), reads the block's [n_groups][32] slab of u (contiguous, 28 KiB at the headline shape: every thread reads 8 keys of one group
+// per pass, all passes in flight at once), forms LB_j = max_g (u_gj + nmin_g) and appends key j to the list of group g iff
+// u_gj + nmax_g >= LB_j (the fp32 addition pass B applies to a logit and its row's statistic: monotone in both arguments, so the test is
+// exact; NaN bounds keep the key).  score_colmax_keys_kernel takes a group's 32 query rows as the A operand and GATHERS 32 of its candidate
+// keys as the B operand (one key per lane), so one 32x32 block of logits serves 32 candidates: ~1.6 blocks per group instead of ~11 pairs,
+// a seventh of the matrix and rounding-chain work.  The logit of a (row, key) pair does not depend on where it sits in an MFMA tile, so the
+// column maxima are the bits of the full pass B.
 constexpr int BD2_THREADS = 256;
 constexpr int BD2_MAXPASS = 8;   // groups per block <= 64 * 8 (host checks)
-template <typename T>
-__global__ __launch_bounds__(BD2_THREADS) void score_bounds2_kernel(ScoreArgs a) {
-    const int kb = blockIdx.x, h = blockIdx.y;
-    const int tid = threadIdx.x;
-    const int oct = tid & 3, grow = tid >> 2;   // 8 keys [8 oct, 8 oct + 8) of group (pass * 64 + grow)
-    __shared__ float s_part[64][33];
-    __shared__ float s_lb8[8][32];
-    __shared__ float s_lb[32];
-    __shared__ uint32_t s_list[64 * BD2_MAXPASS];
-    __shared__ int s_n, s_base, s_poison;
-    if (tid == 0) { s_n = 0; s_poison = 0; }
-    __syncthreads();   // (the flags are initialised before any wave raises s_poison below)
-    const int ng = a.n_groups;
-    const int npass = (ng + 63) / 64;
-    const uint4* ub = reinterpret_cast<const uint4*>(a.colu + ((int64_t)(h * a.nkb + kb) * ng) * 64);   // per group: 8 uint4 (two halves of 32 keys)
-    const float2* gb = a.gbound + (int64_t)h * ng;
-    uint4 uu[BD2_MAXPASS];
-    float2 bb[BD2_MAXPASS];
-#pragma unroll
-    for (int p = 0; p < BD2_MAXPASS; ++p) {
-        const int g = min(p * 64 + grow, ng - 1);
-        if (p < npass) {
-            const uint4 u0 = ub[g * 8 + oct], u1 = ub[g * 8 + 4 + oct];
-            auto pkmax = [](uint32_t x, uint32_t y) __attribute__((always_inline)) -> uint32_t {
-                uint32_t r;
-                if constexpr (std::is_same<T, _Float16>::value) {
-                    asm("v_pk_max_f16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-                } else {   // bf16: no packed maximum - both halves through fp32 (the result is one of the inputs: the way back is exact)
-                    const float lo = fmaxf(pair_lo<T>(x), pair_lo<T>(y)), hi = fmaxf(pair_hi<T>(x), pair_hi<T>(y));
-                    r = (__builtin_bit_cast(uint32_t, lo) >> 16) | (__builtin_bit_cast(uint32_t, hi) & 0xFFFF0000u);
-                }
-                return r;
-            };
-            uu[p] = make_uint4(pkmax(u0.x, u1.x), pkmax(u0.y, u1.y), pkmax(u0.z, u1.z), pkmax(u0.w, u1.w));
-            bb[p] = gb[g];
-        }
-    }
-    constexpr int DT = std::is_same<T, __bf16>::value ? KVZ_BF16 : KVZ_F16;
-    auto key = [&](const uint4& v, int i) __attribute__((always_inline)) -> float {
-        const uint32_t w = (i < 2) ? v.x : (i < 4) ? v.y : (i < 6) ? v.z : v.w;
-        return half_bits_to_float((i & 1) ? (w >> 16) : (w & 0xFFFFu), DT);
-    };
-    float lb[8];
-    bool bad = false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) lb[i] = -INFINITY;
-#pragma unroll
-    for (int p = 0; p < BD2_MAXPASS; ++p) {
-        if (p < npass && p * 64 + grow < ng) {
-            bad |= !(bb[p].x == bb[p].x);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) lb[i] = fmaxf(lb[i], key(uu[p], i) + bb[p].y);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s_part[grow][oct * 8 + i] = lb[i];
-    if (bad) s_poison = 1;
-    __syncthreads();
-    {
-        const int j = tid & 31, part = tid >> 5;
-        float v = -INFINITY;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v = fmaxf(v, s_part[part * 8 + q][j]);
-        s_lb8[part][j] = v;
-    }
-    __syncthreads();
-    if (tid < 32) {
-        float v = -INFINITY;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v = fmaxf(v, s_lb8[q][tid]);
-        s_lb[tid] = v;
-    }
-    __syncthreads();
-    if (s_poison) {
-        if (tid < 32 && kb * 32 + tid < a.m) atomicMin(a.log_out + (int64_t)h * a.log_head_stride + kb * 32 + tid, 0u);
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) lb[i] = s_lb[oct * 8 + i];
-#pragma unroll
-    for (int p = 0; p < BD2_MAXPASS; ++p) {
-        if (p < npass) {   // (uniform: every lane of a quad of threads takes part in the shuffles)
-            const int g = p * 64 + grow;
-            bool c = false;
-            if (g < ng) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float ub1 = key(uu[p], i) + bb[p].x;
-                    c |= (kb * 32 + oct * 8 + i < a.m) && (!(ub1 < lb[i]) || a.all_pairs);
-                }
-            }
-            int ci = c ? 1 : 0;
-            ci |= __shfl_xor(ci, 1, 64);
-            ci |= __shfl_xor(ci, 2, 64);
-            if (ci && oct == 0 && g < ng) s_list[atomicAdd(&s_n, 1)] = (uint32_t)g | ((uint32_t)kb << 11) | ((uint32_t)h << 25);
-        }
-    }
-    __syncthreads();
-    if (tid == 0) s_base = (int)atomicAdd(a.counter + h, (uint32_t)s_n);
-    __syncthreads();
-    uint32_t* const eh = a.entries + (int64_t)h * a.nkb * a.n_groups;
-    for (int i = tid; i < s_n; i += BD2_THREADS) eh[s_base + i] = s_list[i];
-}
-
-// ---- pass B over the candidate pairs only (round 5) ---------------------------------------------------------------------------------
-// No stationary tile, no LDS, no barrier: the list of candidate (32-row group, 32-key block) pairs is cut into equal shares, one per
-// wave; a wave keeps the 32 keys of the current key block in registers (B operand: one KEY per lane, as in the key-per-lane pass A),
-// reads the 32 query rows of a pair straight from memory as the A operand (the rows of the next pair are in flight while this one is
-// computed), and holds ONE running maximum per lane; when the key block changes (or the share ends) the two halves of the wave are
-// merged and the 32 maxima go out with the same atomic minimum on the log-score patterns that merges the row slices of the dense pass.
-constexpr int SB_WAVES = 4;
-#ifndef KVZ_SB_NBUF
-#define KVZ_SB_NBUF 2   // staging buffers per wave of the pair-level sparse pass (knob score_prune = 5)
-#endif
-#ifndef KVZ_SB_OCC1
-#define KVZ_SB_OCC1 3   // blocks per CU of the one-buffer sparse pass (4: 128 registers per lane - two of them spill)
-#endif
-// log-score of four logits: t_k = float(x_k) + n_k (fp16: the mixed-precision fma reads the 16-bit half and adds in one instruction -
-// x * 1.0 + n is the same single rounding as the conversion followed by the addition)
-template <typename T>
-__device__ static inline void quad_addn(uint32_t xa, uint32_t xb, float n0, float n1, float n2, float n3, float (&t)[4]) {
-    if constexpr (std::is_same<T, _Float16>::value) {
-        asm("v_fma_mix_f32 %[t0], %[xa], 1.0, %[n0] op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mix_f32 %[t2], %[xb], 1.0, %[n2] op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mix_f32 %[t1], %[xa], 1.0, %[n1] op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mix_f32 %[t3], %[xb], 1.0, %[n3] op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-            : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3])
-            : [xa] "v"(xa), [xb] "v"(xb), [n0] "v"(n0), [n1] "v"(n1), [n2] "v"(n2), [n3] "v"(n3));
-    } else {
-        t[0] = pair_lo<T>(xa) + n0; t[1] = pair_hi<T>(xa) + n1; t[2] = pair_lo<T>(xb) + n2; t[3] = pair_hi<T>(xb) + n3;
-    }
-}
-// NBUF = 2 (round 5): a wave stages the rows of the next pair into its second buffer while it computes the current one; 67 KiB of LDS per
-// block: two blocks = eight waves per CU.  NBUF = 1 (round 6): ONE buffer per wave - the rows of the next pair are staged into it as soon
-// as the fragments of the current pair sit in registers (before its MFMAs: the same distance ahead), half the LDS, SIXTEEN waves per CU.
-template <typename T, int D, bool FAST, int NBUF>
-__global__ __launch_bounds__(SB_WAVES * 64, NBUF == 1 ? KVZ_SB_OCC1 : 2) void score_colmax_sparse_kernel(ScoreArgs a) {
-    typedef ScoreCfg<D> C;
-    typedef typename Mfma32<T>::v8 v8;
-    constexpr int QG_BYTES = 32 * C::ROW_BYTES;      // the 32 query rows of a pair, swizzled like a key tile
-    constexpr int PB_BYTES = QG_BYTES + 256;         // + their 32 statistics n_r (written twice: one 64-lane dword DMA)
-    __shared__ __attribute__((aligned(16))) char lds[SB_WAVES * NBUF * PB_BYTES];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int l31 = lane & 31, half = lane >> 5;
-    const int R = a.G * a.q_len;
-    // the heads' lists, one after the other, cut into equal shares; blocks are dispatched round-robin over the 8 XCDs: the blocks of one XCD
-    // take one contiguous eighth of the pairs (a head's query rows and keys stay in that XCD's L2)
-    const uint32_t cnt_l = (lane < a.n_kv_heads) ? a.counter[lane] : 0u;   // (Hkv < 128: lanes 0..63 hold heads 0..63, the second word below)
-    const uint32_t cnt_h = (lane + 64 < a.n_kv_heads) ? a.counter[lane + 64] : 0u;
-    auto head_count = [&](int hh) __attribute__((always_inline)) -> int {
-        return hh < 64 ? __builtin_amdgcn_readlane((int)cnt_l, hh) : __builtin_amdgcn_readlane((int)cnt_h, hh - 64);
-    };
-    int total = 0;
-    for (int hh = 0; hh < a.n_kv_heads; ++hh) total += head_count(hh);
-    const int nb8 = (int)gridDim.x >> 3;
-    const int lb = (nb8 > 0 && (gridDim.x & 7u) == 0) ? (int)(blockIdx.x & 7u) * nb8 + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int W = gridDim.x * SB_WAVES, w = lb * SB_WAVES + wave;
-    const int per = (total + W - 1) / W;
-    const int lo = w * per, hi = min(total, lo + per);
-    if (lo >= hi) return;
-    const int64_t head_cap = (int64_t)a.nkb * a.n_groups;
-    const f16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    char* const wl = lds + wave * NBUF * PB_BYTES;
-    const uint32_t wl0 = lds_addr(wl);
-    FragAddr<D> fa0;
-    fa0.init(wl, l31, half);
-    const uint32_t nb0 = wl0 + (uint32_t)QG_BYTES + (uint32_t)(4 * half) * 4u;   // + 32 qd: the statistics of accumulators 4 qd .. 4 qd + 3
-
-    // rows and statistics of pair e -> LDS buffer b of this wave (9 DMA instructions, nothing through registers)
-    constexpr int ROWS_PER_INSTR = 1024 / C::ROW_BYTES;
-    const int lrow = lane / C::CPR, pch = lane % C::CPR;
-    const int64_t hs = a.q_head_stride * 2;
-    auto stage = [&](int b, uint32_t e) __attribute__((always_inline)) {
-        const int g = (int)(e & 2047u), h = (int)(e >> 25);
-        const char* qh = reinterpret_cast<const char*>(a.q) + (int64_t)h * a.G * hs;
-        const uint32_t buf = wl0 + (uint32_t)(b * PB_BYTES);
-        const int rc0 = min(g * 32, R - 1);
-        const int g0 = a.dq.div(rc0), qi0 = rc0 - g0 * a.q_len;   // (wave-uniform; q_len >= 32: at most two query heads per group)
-        const uint32_t base = (uint32_t)(g0 * (int)hs + qi0 * C::ROW_BYTES);
-        const uint32_t wrapd = (uint32_t)((int)hs - a.q_len * C::ROW_BYTES);
-        const int nfirst = a.q_len - qi0, tail = R - 1 - rc0;
-#pragma unroll
-        for (int i = 0; i < 32 / ROWS_PER_INSTR; ++i) {
-            const int row = i * ROWS_PER_INSTR + lrow;
-            const int chunk = (D == 128) ? (pch ^ (row & 15)) : (pch ^ ((row >> 1) & 7));
-            const int rowc = min(row, tail);
-            const uint32_t voff = base + (uint32_t)(rowc * C::ROW_BYTES + chunk * 16) + (rowc >= nfirst ? wrapd : 0u);
-            lds_dma16a(qh, voff, buf + (uint32_t)(i * 1024));
-        }
-        {
-            const char* np = reinterpret_cast<const char*>(a.nrow + ((int64_t)h * a.n_groups + g) * 32);
-            const uint32_t la = __builtin_amdgcn_readfirstlane(buf + (uint32_t)QG_BYTES);
-            const uint64_t bs = (uint64_t)(uintptr_t)np;
-            const uint64_t bss = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(bs >> 32)) << 32) |
-                                 (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)bs);
-            const uint32_t voff = (uint32_t)(l31 * 4);
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(bss), "s"(la) : "memory");
-        }
-    };
-    constexpr int STAGE_OPS = 32 / ROWS_PER_INSTR + 1;
-
-    u32x4 bk[C::KK];
-    uint32_t cur = 0xFFFFFFFFu;   // (h, kb) of the keys in bk
-    float best = -INFINITY;
-    auto flush = [&]() __attribute__((always_inline)) {
-        const int kb = (int)(cur & 0x3FFFu), h = (int)(cur >> 14);
-        const uint32_t bb = __builtin_bit_cast(uint32_t, best);
-        const auto sw = __builtin_amdgcn_permlane32_swap(bb, bb, false, false);
-        const float b = fmaxf(__builtin_bit_cast(float, (uint32_t)sw[0]), __builtin_bit_cast(float, (uint32_t)sw[1]));
-        const int j = kb * 32 + l31;
-        if (half == 0 && j < a.m) {
-            const uint32_t enc = (b >= 0.f) ? 1u : __builtin_bit_cast(uint32_t, b);   // (the encoding of the dense pass; NaN cannot come here)
-            atomicMin(a.log_out + (int64_t)h * a.log_head_stride + j, enc);
-        }
-    };
-    auto keys_for = [&](uint32_t e) __attribute__((always_inline)) {
-        const uint32_t hk = e >> 11;
-        if (hk != cur) {
-            if (cur != 0xFFFFFFFFu) flush();
-            cur = hk;
-            best = -INFINITY;
-            const int kb = (int)(hk & 0x3FFFu), h = (int)(hk >> 14);
-            const int j = min(kb * 32 + l31, a.m - 1);
-            const char* kp = reinterpret_cast<const char*>(a.k) + ((int64_t)h * a.k_head_stride + (int64_t)(a.start + j) * D) * 2 + half * 16;
-#pragma unroll
-            for (int kk = 0; kk < C::KK; ++kk) bk[kk] = *reinterpret_cast<const u32x4*>(kp + kk * 32);
-        }
-    };
-    typedef float f4v __attribute__((ext_vector_type(4)));
-    typedef const __attribute__((address_space(3))) f4v* lds_f4_t;
-    auto compute = [&](auto b_tag, auto&& restage) __attribute__((always_inline)) {
-        constexpr int B = decltype(b_tag)::value;
-        u32x4 fq[C::KK];
-        frag_load<D>(fq, fa0, B * PB_BYTES);
-        f4v nn[4];
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) nn[qd] = *(lds_f4_t)(uintptr_t)(nb0 + (uint32_t)(B * PB_BYTES + 32 * qd));
-        if constexpr (NBUF == 1) {   // the buffer is free once the reads have returned: the rows of the next pair go into it now
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            restage();
-        }
-        f16v acc = zero16;
-#pragma unroll
-        for (int kk = 0; kk < C::KK; ++kk) acc = Mfma32<T>::mfma(__builtin_bit_cast(v8, fq[kk]), __builtin_bit_cast(v8, bk[kk]), acc);
-        // the rounding chain is an assembly block: the compiler does not count the wait states between the last MFMA of the chain and the
-        // first read of its result (18 for a 16-pass MFMA) - the first quad read stale accumulators without them
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-            uint32_t xa, xb;
-            quad_round<T, FAST>(acc[4 * qd], acc[4 * qd + 1], acc[4 * qd + 2], acc[4 * qd + 3], xa, xb, a.c, a.rcp);
-            // accumulators 4 qd .. 4 qd + 3 are rows 8 qd + 4 half + (0..3)
-            float t[4];
-            quad_addn<T>(xa, xb, nn[qd].x, nn[qd].y, nn[qd].z, nn[qd].w, t);
-            best = fmaxf(fmaxf(best, t[0]), t[1]);   // (two v_max3_f32)
-            best = fmaxf(fmaxf(best, t[2]), t[3]);
-        }
-    };
-    typedef std::integral_constant<int, 0> I0;
-    typedef std::integral_constant<int, 1> I1;
-    // the share in batches of 64 pairs: one entry per lane, read with v_readlane (a load the compiler sees inside the loop would make it
-    // wait for everything in flight, the staged rows of the next pair included)
-    // (a batch lies inside one head's list)
-    int hcur = 0, hbase = 0;   // head of position b0, global position of its first pair
-    for (int b0 = lo; b0 < hi;) {
-        while (b0 >= hbase + head_count(hcur)) { hbase += head_count(hcur); ++hcur; }
-        const int nb = min(min(64, hi - b0), hbase + head_count(hcur) - b0);
-        const uint32_t ev = a.entries[hcur * head_cap + (b0 - hbase) + min(lane, nb - 1)];
-        auto entry = [&](int i) __attribute__((always_inline)) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)ev, i); };
-        stage(0, entry(0));
-        if constexpr (NBUF == 1) {
-            for (int i = 0; i < nb; ++i) {
-                keys_for(entry(i));   // (a key block's loads are issued before the wait for the staged rows: one round trip, not two)
-                stage_wait();
-                compute(I0{}, [&]() __attribute__((always_inline)) { if (i + 1 < nb) stage(0, entry(i + 1)); });
-            }
-        } else {
-            auto none = [&]() __attribute__((always_inline)) {};
-            for (int i = 0; i < nb; i += 2) {
-                const bool has1 = i + 1 < nb;
-                if (has1) stage(1, entry(i + 1));
-                keys_for(entry(i));
-                if (has1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(STAGE_OPS) : "memory");
-                else stage_wait();
-                compute(I0{}, none);
-                if (!has1) break;
-                const bool has2 = i + 2 < nb;
-                if (has2) stage(0, entry(i + 2));
-                keys_for(entry(i + 1));
-                if (has2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(STAGE_OPS) : "memory");
-                else stage_wait();
-                compute(I1{}, none);
-            }
-        }
-        b0 += nb;
-    }
-    flush();
-}
-
-// ---- candidates at KEY granularity (round 6) ------------------------------------------------------------------------------------------------
-// A (32-row group, 32-key block) pair is recomputed in full - 1024 logits - although all it is needed for is, typically, ONE key: every key
-// has its argmax group (and the one or two groups whose bound cannot rule them out), so a key block of 32 keys names ~55 of the 448 groups
-// (18 % of the pairs on the benchmark's inputs).  Turned around, a row group is named by ~31 KEYS of the whole chunk: score_bounds3_kernel
-// applies the same exact test per (group, key) - u_gj + nmax_g >= LB_j - and appends key j to the list of group g; score_colmax_keys_kernel
-// takes a group's 32 query rows as the A operand and GATHERS 32 of its candidate keys as the B operand (one key per lane), so one 32x32
-// block of logits serves 32 candidates: ~1.6 blocks per group instead of ~11 pairs, a seventh of the matrix and rounding-chain work.  The
-// logit of a (row, key) pair does not depend on where it sits in an MFMA tile, so the column maxima are the bits of the full pass B.
 struct Bounds3Smem {
     float part[64][33];
     float lb8[8][32];
@@ -2718,7 +2373,8 @@ __global__ __launch_bounds__(BD2_THREADS) void score_bounds3_kernel(ScoreArgs a)
 }
 
 // The work items - (KV head, row group, chunk of 32 candidate keys), announced by score_bounds3_kernel in per-head queues - are cut into equal
-// shares, one per wave (the blocks of one XCD take one contiguous eighth, as in the pair-level kernel).  Per item: the group's 32 query rows
+// shares, one per wave (blocks are dispatched round-robin over the 8 XCDs: the blocks of one XCD take one contiguous eighth of the items, so
+// a head's query rows and keys stay in that XCD's L2).  Per item: the group's 32 query rows
 // are staged into the wave's LDS buffer (LDS-DMA, swizzled like a key tile) and read into registers as the A operand; the chunk's keys are
 // gathered as the B operand - lane (j, half) loads the eight 16-byte chunks of ITS key row straight from the cache - and one chain of MFMAs
 // gives every lane the logits of its key against 16 of the rows; rounding chain, x + n_r, maximum over the lane's rows, the two halves
@@ -2733,6 +2389,21 @@ template <int D> struct SkSmem {
     static constexpr int PB_BYTES = QG_BYTES + 256;                   // + their 32 statistics n_r (written twice: one 64-lane dword DMA)
     static constexpr int BYTES = SK_WAVES * PB_BYTES;
 };
+// log-score of four logits: t_k = float(x_k) + n_k (fp16: the mixed-precision fma reads the 16-bit half and adds in one instruction -
+// x * 1.0 + n is the same single rounding as the conversion followed by the addition)
+template <typename T>
+__device__ static inline void quad_addn(uint32_t xa, uint32_t xb, float n0, float n1, float n2, float n3, float (&t)[4]) {
+    if constexpr (std::is_same<T, _Float16>::value) {
+        asm("v_fma_mix_f32 %[t0], %[xa], 1.0, %[n0] op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mix_f32 %[t2], %[xb], 1.0, %[n2] op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mix_f32 %[t1], %[xa], 1.0, %[n1] op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mix_f32 %[t3], %[xb], 1.0, %[n3] op_sel:[1,0,0] op_sel_hi:[1,0,0]"
+            : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3])
+            : [xa] "v"(xa), [xb] "v"(xb), [n0] "v"(n0), [n1] "v"(n1), [n2] "v"(n2), [n3] "v"(n3));
+    } else {
+        t[0] = pair_lo<T>(xa) + n0; t[1] = pair_hi<T>(xa) + n1; t[2] = pair_lo<T>(xb) + n2; t[3] = pair_hi<T>(xb) + n3;
+    }
+}
 // (block bid of nblk: the stand-alone launch passes its own index and grid, the fused tail launch the index inside its candidate-key part)
 template <typename T, int D, bool FAST>
 __device__ static inline void score_colmax_keys_body(const ScoreArgs& a, const uint32_t bid, const uint32_t nblk, char* const lds) {
@@ -3170,60 +2841,21 @@ static int launch_score_impl(ScoreArgs a, int Hkv, hipStream_t stream, TailState
     a.max_seg = plan.max_seg;
     a.row_splits = score_row_splits(Hkv, a.G, a.q_len, a.m);
     const int ctiles = (a.m + PB_COLS - 1) / PB_COLS;
-    // exact pruning of pass B (round 5; knob score_prune: 0 = two full passes; 1 = key-per-lane pass A, every block of pass B (checks);
-    // 3 = candidate pairs only; 4 = every pair through the sparse kernel (checks)).  Both dtypes (round 6); deferred-log path.
+    // pass A and pass B by the knob score_prune (kvz_api.hip): 0 = two full passes; 1 = key-per-lane pass A, the full pass B (check);
+    // 3 = key-per-lane pass A, merge, bounds, candidate keys; 4 = 3 with every (group, key) pair a candidate (check); 6 (default) = 3 with
+    // merge, bounds and candidate keys pipelined over the calls of a stream (asynchronous entry points only).  Both dtypes; deferred-log path.
     int prune = 0;
     if (a.unit_nseg && prune_shape_ok(a.n_groups, a.nkb, Hkv, a.q_len)) prune = tunable(TUNE_SCORE_PRUNE);
-    if (prune >= 3 && !a.log_out) prune = 1;   // (the sparse pass merges through the log buffer)
+    if (prune >= 3 && !a.log_out) prune = 1;   // (the candidate-key pass merges through the log buffer)
     if (tail && prune != 6) {
         set_error("kvz_score_chunk: internal - a pipelined tail without the knob");
         return KVZ_EINVAL;
     }
-    if (prune == 6 && !tail) prune = 3;        // (6 = 3 with the tail pipelined over the calls of a stream: asynchronous entry points only)
-    if (prune) {
-        {
-            ProfScope ps("score_rowstat", stream);
-            hipLaunchKernelGGL((score_rowstatT2_kernel<T, D, FAST>), dim3(plan.nb), dim3(PA_WAVES * 64), 0, stream, a, plan);
-            KVZ_CHECK_LAUNCH("score_rowstatT2_kernel");
-        }
-        if (prune == 6) {
-            a.all_pairs = 0;
-            return launch_tail<T, D, FAST>(&a, *tail);
-        }
-        if (prune >= 3) {
-            a.all_pairs = (prune == 4);
-            if (prune != 5) {   // candidates at key granularity (round 6)
-                // (measurement only, results unusable: score_prune = 16 + mask leaves launches out - 1: the merge, 2: the bounds, 4: the candidate-key pass)
-                const int skip = prune >= 16 ? (prune & 7) : 0;
-                {
-                    ProfScope ps("score_bounds", stream);
-                    if (!(skip & 1)) hipLaunchKernelGGL(score_merge_kernel, dim3((a.G * a.q_len + PA_ROWS - 1) / PA_ROWS * Hkv), dim3(PA_ROWS), 0, stream, a);
-                    KVZ_CHECK_LAUNCH("score_merge_kernel");
-                    if (!(skip & 2)) hipLaunchKernelGGL((score_bounds3_kernel<T>), dim3(a.nkb, Hkv), dim3(BD2_THREADS), 0, stream, a);
-                    KVZ_CHECK_LAUNCH("score_bounds3_kernel");
-                }
-                if (!(skip & 4)) {
-                    ProfScope ps("score_colmax", stream);
-                    // (four blocks = sixteen waves per CU: an item is mostly latency - queue entry, candidate index, key row - and there are ~1.6 per (head, group))
-                    hipLaunchKernelGGL((score_colmax_keys_kernel<T, D, FAST>), dim3(KVZ_SK_BLOCKS_PER_CU * device_cus()), dim3(SK_WAVES * 64), 0, stream, a);
-                    KVZ_CHECK_LAUNCH("score_colmax_keys_kernel");
-                }
-                return KVZ_OK;
-            }
-            {
-                ProfScope ps("score_bounds", stream);
-                hipLaunchKernelGGL(score_merge_kernel, dim3((a.G * a.q_len + PA_ROWS - 1) / PA_ROWS * Hkv), dim3(PA_ROWS), 0, stream, a);
-                KVZ_CHECK_LAUNCH("score_merge_kernel");
-                hipLaunchKernelGGL((score_bounds2_kernel<T>), dim3(a.nkb, Hkv), dim3(BD2_THREADS), 0, stream, a);
-                KVZ_CHECK_LAUNCH("score_bounds2_kernel");
-            }
-            {
-                ProfScope ps("score_colmax", stream);
-                hipLaunchKernelGGL((score_colmax_sparse_kernel<T, D, FAST, KVZ_SB_NBUF>), dim3((KVZ_SB_NBUF == 1 ? KVZ_SB_OCC1 : 2) * device_cus()), dim3(SB_WAVES * 64), 0, stream, a);
-                KVZ_CHECK_LAUNCH("score_colmax_sparse_kernel");
-            }
-            return KVZ_OK;
-        }
+    if (prune == 6 && !tail) prune = 3;
+    if (prune != 0) {
+        ProfScope ps("score_rowstat", stream);
+        hipLaunchKernelGGL((score_rowstatT2_kernel<T, D, FAST>), dim3(plan.nb), dim3(PA_WAVES * 64), 0, stream, a, plan);
+        KVZ_CHECK_LAUNCH("score_rowstatT2_kernel");
     } else if (a.unit_nseg) {  // (null: the row statistics came out of the scoring forward's attention kernel - kvz_flash_fwd_window)
         ProfScope ps("score_rowstat", stream);
         hipLaunchKernelGGL((score_rowstat2_kernel<T, D, FAST>), dim3(plan.nb), dim3(PA_WAVES * 64), 0, stream, a, plan);
@@ -3231,6 +2863,28 @@ static int launch_score_impl(ScoreArgs a, int Hkv, hipStream_t stream, TailState
     } else {
         a.max_seg = 1;
     }
+    if (prune == 6) {
+        a.all_pairs = 0;
+        return launch_tail<T, D, FAST>(&a, *tail);
+    }
+    if (prune == 3 || prune == 4) {
+        a.all_pairs = (prune == 4);
+        {
+            ProfScope ps("score_bounds", stream);
+            hipLaunchKernelGGL(score_merge_kernel, dim3((a.G * a.q_len + PA_ROWS - 1) / PA_ROWS * Hkv), dim3(PA_ROWS), 0, stream, a);
+            KVZ_CHECK_LAUNCH("score_merge_kernel");
+            hipLaunchKernelGGL((score_bounds3_kernel<T>), dim3(a.nkb, Hkv), dim3(BD2_THREADS), 0, stream, a);
+            KVZ_CHECK_LAUNCH("score_bounds3_kernel");
+        }
+        {
+            ProfScope ps("score_colmax", stream);
+            // (four blocks = sixteen waves per CU: an item is mostly latency - queue entry, candidate index, key row - and there are ~1.6 per (head, group))
+            hipLaunchKernelGGL((score_colmax_keys_kernel<T, D, FAST>), dim3(KVZ_SK_BLOCKS_PER_CU * device_cus()), dim3(SK_WAVES * 64), 0, stream, a);
+            KVZ_CHECK_LAUNCH("score_colmax_keys_kernel");
+        }
+        return KVZ_OK;
+    }
+    // 0 and 1: the full pass B
     {
         ProfScope ps("score_colmax", stream);
         hipLaunchKernelGGL((score_colmax3_kernel<T, D, FAST>), dim3(ctiles * a.row_splits * Hkv), dim3(PB_WAVES * 64), 0, stream, a);

@@ -71,6 +71,19 @@ def test_host_only_entry_points():
         assert prev == 1 and lib.kvz_flash_workspace_bytes(4, 7, 2026, 128) == 0     # enough units by themselves, nothing to merge
     finally:
         lib.kvz_debug_set_tunable(b"flash2_split", prev)
+    # score_prune takes 0 / 1 / 3 / 4 / 6 (negative: the default, 6); any other value is rejected and leaves the knob as it was
+    prev = lib.kvz_debug_get_tunable(b"score_prune")
+    try:
+        lib.kvz_debug_set_tunable(b"score_prune", 3)
+        for v in (5, 2, 16):
+            assert lib.kvz_debug_set_tunable(b"score_prune", v) == -1 and b"score_prune" in lib.kvz_last_error()
+            assert lib.kvz_debug_get_tunable(b"score_prune") == 3
+        for v in (0, 1, 3, 4, 6):
+            assert lib.kvz_debug_set_tunable(b"score_prune", v) >= 0 and lib.kvz_debug_get_tunable(b"score_prune") == v
+        lib.kvz_debug_set_tunable(b"score_prune", 3)
+        assert lib.kvz_debug_set_tunable(b"score_prune", -1) == 3 and lib.kvz_debug_get_tunable(b"score_prune") == 6
+    finally:
+        lib.kvz_debug_set_tunable(b"score_prune", prev)
     # asynchronous-scoring contexts are host objects (events): creating / destroying them needs no kernel
     assert lib.kvz_async_create(0) < 0 and b"slot" in lib.kvz_last_error()
     assert lib.kvz_async_wait(12345, -1, None) < 0 and lib.kvz_async_destroy(12345) == 0

@@ -9,7 +9,7 @@ pass, a tie decided the wrong way, moves a score that is compared bit for bit.
 Entry points: kvz_score_chunk (ops.score_chunk), kvz_score_chunk_log + kvz_score_finalize_log, kvz_score_finalize_log_hist +
 kvz_select_threshold_prehist, kvz_score_chunk_async_log, kvz_update_score_async_log, the pipelined tail (knob 6, a workspace of three
 sets, kvz_score_tail_flush in the middle) and kvz_score_from_stats_log on the statistics of kvz_flash_fwd_window.  Knobs: score_prune
-0 / 1 / 3 / 4 / 5 / 6 and the two-pass path of q_len < 32.  Every knob is restored in `finally`."""
+0 / 1 / 3 / 4 / 6 and the two-pass path of q_len < 32.  Every knob is restored in `finally`."""
 import contextlib
 import functools
 
@@ -42,7 +42,7 @@ GEOMS = {
     "m33_q257": (2, 7, 64, 4, 4, 33, 257, 0, 4),
     "m5_q257": (1, 1, 128, 32, 32, 5, 257, 0, 0),
 }
-LOG_KNOBS = (0, 1, 3, 4, 5)
+LOG_KNOBS = (0, 1, 3, 4)
 
 
 @functools.lru_cache(maxsize=8)

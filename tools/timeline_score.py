@@ -1,11 +1,11 @@
 #!/usr/bin/env python
 """Timeline of the scoring loop from a rocprofv3 --kernel-trace csv (…_kernel_trace.csv): how long the dominant pass-A kernels run, what
-sits between the end of one and the start of the next, and which small launches (merge / bounds / sparse pass) run there.
+sits between the end of one and the start of the next, and which small launches (merge / bounds / candidate-key pass) run there.
    python tools/timeline_score.py <kernel_trace.csv> [first_row_of_sample]"""
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
 def short(n):
-    for k in ("score_rowstatT2", "score_rowstat2", "score_tail", "score_merge", "score_bounds2", "score_bounds3", "score_colmax_sparse", "score_colmax_keys", "score_colmax3", "dense_append", "finalize"):
+    for k in ("score_rowstatT2", "score_rowstat2", "score_tail", "score_merge", "score_bounds3", "score_colmax_keys", "score_colmax3", "dense_append", "finalize"):
         if k in n: return k
     return n.split("(")[0][-28:]
 ev = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"]), r.get("Queue_Id", "?")) for r in rows), key=lambda x: x[0])
