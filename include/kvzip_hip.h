@@ -383,6 +383,45 @@ int kvz_flash_fwd(const void* q, int64_t q_stride_head, int64_t q_stride_group, 
                   void* out, int64_t o_stride_head, int64_t o_stride_group, int64_t o_stride_pos,
                   float* lse_out, void* ws, size_t ws_bytes, kvz_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ * Forked decode: B concurrent queries ("branches") over ONE shared pruned cache.
+ * No reference counterpart: batch is 1 there (every query of a context is answered after the other, eval.py / model/wrapper.py:251-284),
+ * so B answers read every kept K,V row B times; here the shared rows are read once per step whatever B is.
+ *
+ * Decode step, one new token per active branch:
+ *   q            : [B, Hkv, G, D]                       out : [B, Hkv, G, D]
+ *   k_cache, v_cache : the flat cache [rows, D], READ-ONLY; head h owns rows k_start[h] .. + k_len[h] + k_len_offset (device arrays,
+ *                  or k_meta_host = {start[Hkv], len[Hkv]} by value; either may be NULL if the other is given; k_len_offset = rows
+ *                  appended to every head before the fork)
+ *   tail_k, tail_v : [B, Hkv, tail_cap, D] private rows of the branches (query tokens, generated tokens)
+ *   tail_len_host : HOST int32[B], rows in use per branch BEFORE this call, passed to the kernel by value; -1 = inactive branch
+ *                  (no write, its output rows are zero).  Every value must be < tail_cap.
+ *   k_new, v_new : [B, Hkv, 1, D] views (batch and head strides in elements, multiples of 8; D contiguous)
+ * For an active branch b and head h the new row is written to tail[b, h, tail_len[b]]; the query rows (b, h, .) attend to ALL keys
+ * of head h's shared segment (no causal mask: the whole context precedes every query) and to tail rows 0 .. tail_len[b] of branch b
+ * (the new one included), and to nothing of another branch.  P = softmax(q.k^T * scale) in fp32, out = P.v rounded once.
+ * Limits: D in {64, 128}, B <= 16, B*G <= 64 query rows per KV head, Hkv <= 64 (KVZ_EUNSUPPORTED otherwise).
+ * ws: kvz_fork_attn_workspace_bytes(...) bytes, no initialisation needed; the size does not depend on max_len_k; 0 for B <= 0.
+ * ------------------------------------------------------------------------- */
+size_t kvz_fork_attn_workspace_bytes(int B, int Hkv, int G, int D, int max_len_k);
+int kvz_fork_attn_append(const void* q, const void* k_cache, const void* v_cache,
+                         const int32_t* k_start, const int32_t* k_len, int k_len_offset, const int32_t* k_meta_host,
+                         void* tail_k, void* tail_v, int tail_cap, const int32_t* tail_len_host,
+                         const void* k_new, const void* v_new,
+                         int64_t k_new_batch_stride, int64_t k_new_head_stride,
+                         int64_t v_new_batch_stride, int64_t v_new_head_stride,
+                         int B, int Hkv, int G, int D, float scale, int dtype,
+                         void* out, void* ws, size_t ws_bytes, kvz_stream_t stream);
+
+/* Merge of two partial attention results over disjoint key sets by their LSEs (no reference counterpart: batch is 1 there and a
+ * query's keys live in one cache).  A branch's first step (q_len > 1) is kvz_flash_fwd over the shared segments (causal = 0) and over
+ * the branch's tail (causal = 1), each with lse_out, then this call:
+ *   m = max(lse1, lse2);  w_i = exp(lse_i - m);  out[r, :] = (w1*o1[r, :] + w2*o2[r, :]) / (w1 + w2);  both -inf -> 0
+ * o1, o2, out: [rows, D] contiguous, 16-bit; lse1, lse2: float [rows] (natural log, -inf = the row saw no key; that side's values
+ * are then ignored whatever they hold).  out may alias o1 or o2.  D in {64, 128}. */
+int kvz_attn_merge_lse(const void* o1, const float* lse1, const void* o2, const float* lse2, void* out,
+                       int64_t rows, int D, int dtype, kvz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,10 @@ SIGNATURES = {
     "kvz_flash_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "kvz_flash_fwd": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _i64, _i64,
                            _i64, _vp, _vp, _sz, _vp]),
+    "kvz_fork_attn_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "kvz_fork_attn_append": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i,
+                                  _f, _i, _vp, _vp, _sz, _vp]),
+    "kvz_attn_merge_lse": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,622 @@
+// kvz_fork.hip — forked decode: B concurrent queries (branches) over ONE shared pruned KV cache, gfx950.
+//
+// No reference counterpart: the reference decodes one query at a time (batch is hard-wired to 1), so B answers
+// read every kept K and V row B times.  Here every branch owns a small private TAIL ([B, Hkv, tail_cap, D]: the K,V of its query
+// tokens and of the tokens it generates) and all branches share the flat cache read-only.  One decode step:
+//   fork_attn_kernel     grid.x = B*Hkv tail items ++ the shared work items, cut from the SUM of the ragged head lengths exactly as
+//                        varlen_attn_split2_kernel cuts them.  The R = B*G query rows of a head (row = b*G + g) form ceil(R/16) row
+//                        tiles; a block keeps the K fragments and the staged V tile of a 32-key wave tile and applies them to the
+//                        NT row tiles it owns (Q fragments, softmax state and accumulators per row tile in registers), so the shared
+//                        rows come from HBM once per step whatever B is (NT = 2: four row tiles are two blocks, grid.y = 2 - the 256
+//                        registers a lane of an 8-wave block has do not hold four sets of accumulators).  A tail item (b, h) first
+//                        writes the branch's new K,V row to tail[b, h, tail_len[b]] (only this block reads that row; block-scope
+//                        barrier before the read) and attends the G rows of (b, h) over tail rows 0 .. tail_len[b].
+//   fork_combine_kernel  per (branch, head, group row): merges the partials of the head's key ranges and of the branch's tail.
+//                        Final normalisation: out = fp16/bf16(a / l)  (the 'div' form of tests/attn_probes.py, like the decode combine
+//                        of kvz_attn.hip); rows of an inactive branch (tail_len[b] < 0) are zero.
+// No causal mask on the shared part: the whole context precedes every query.  The shared cache is never written.
+//
+// attn_merge_lse_kernel: merges two partial attention results by their natural-log LSEs (a branch's first step: kvz_flash_fwd over the
+// shared segments, causal = 0, and over the branch's tail, causal = 1):
+//   m = max(lse1, lse2);  w_i = exp(lse_i - m);  out = fp16/bf16((w1*o1 + w2*o2) / (w1 + w2));  both -inf -> 0.
+#include "kvz_common.h"
+
+#include <type_traits>
+
+namespace kvz {
+namespace fork {
+
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef __bf16 b8 __attribute__((ext_vector_type(8)));
+typedef short s4 __attribute__((ext_vector_type(4)));
+typedef short s8 __attribute__((ext_vector_type(8)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <typename T> struct Half;
+template <> struct Half<_Float16> {
+    typedef h8 v8;
+    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+};
+template <> struct Half<__bf16> {
+    typedef b8 v8;
+    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+};
+
+constexpr int FK_THREADS = 512;
+constexpr int FK_WAVES = 8;
+constexpr int FK_KT = 32;            // keys per wave tile
+constexpr int FK_RT = 16;            // query rows per row tile (MFMA N)
+constexpr int FK_MAXH = 64;
+constexpr int FK_MAXB = 16;
+constexpr int FK_MAXROWS = 64;       // B*G
+
+template <int D> struct Cfg {
+    static constexpr int ROW_BYTES = D * 2;
+    static constexpr int VSTRIDE = ROW_BYTES + 32;          // padded LDS row: conflict-free tr reads
+    static constexpr int WAVE_LDS = FK_KT * VSTRIDE;        // bytes of V staging per wave
+    static constexpr int KK = D / 32;
+    static constexpr int DB = D / 16;
+    static constexpr int CPR = ROW_BYTES / 16;
+    static constexpr int VLOADS = FK_KT * CPR / WAVE;
+};
+
+struct HeadMeta { int32_t start[FK_MAXH]; int32_t len[FK_MAXH]; };
+struct TailLens { int32_t n[FK_MAXB]; };
+
+// the key-range cut of the shared part (the same arithmetic in both kernels)
+__device__ static inline int chunk_of(int total, int target_items) {
+    int chunk = (total + target_items - 1) / target_items;
+    chunk = (chunk + 127) / 128 * 128;
+    return chunk < 128 ? 128 : chunk;
+}
+
+template <typename T, int D, int NT>
+__global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const int32_t* __restrict__ k_start,
+    const int32_t* __restrict__ k_len, int k_len_offset, HeadMeta hm, int host_meta, T* tail_k, T* tail_v, int tail_cap, TailLens tl,
+    const T* __restrict__ k_new, const T* __restrict__ v_new, int64_t kn_bstride, int64_t kn_hstride, int64_t vn_bstride,
+    int64_t vn_hstride, int B, int Hkv, int G, int target_items, float scale, float* __restrict__ part_o,
+    float* __restrict__ part_ml, float* __restrict__ tail_o, float* __restrict__ tail_ml, int n_rtiles) {
+    typedef Cfg<D> C;
+    typedef typename Half<T>::v8 v8;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int l15 = lane & 15, quad = lane >> 4;
+    const int R = B * G;
+    const int GT = (G + FK_RT - 1) / FK_RT;   // row tiles of ONE branch (tail items)
+    const int TG = (GT + NT - 1) / NT;        // blocks of one tail item: one unless a single branch has more than 16 * NT rows
+    const int n_tail = B * Hkv * TG;
+
+    // ---- this block's work item (wave-uniform scalar work) ----
+    int h, len, c0, c1, branch = -1, grp = 0;
+    int64_t slot0;                 // first partial row of row tile 0 of this item (+ 16 per row tile)
+    const char *kbase, *vbase;
+    float *po, *pml;
+    if ((int)blockIdx.x < n_tail) {
+        if (blockIdx.y != 0) return;
+        grp = blockIdx.x % TG;
+        branch = (blockIdx.x / TG) / Hkv;
+        h = blockIdx.x / TG - branch * Hkv;
+        const int t = tl.n[branch];
+        if (t < 0) return;         // inactive branch: nothing written, the combine emits zeros
+        const int64_t row0 = ((int64_t)branch * Hkv + h) * tail_cap;
+        constexpr int CH = D * 2 / 16;
+        // the branch's new row: only this block reads it (G > 16 * NT, one branch: each of the item's blocks writes the same bytes and
+        // reads its own copy behind its own barrier)
+        if ((int)threadIdx.x < 2 * CH) {
+            const bool is_v = (int)threadIdx.x >= CH;
+            const int c = (int)threadIdx.x - (is_v ? CH : 0);
+            const char* src = reinterpret_cast<const char*>(is_v ? v_new + branch * vn_bstride + h * vn_hstride
+                                                                 : k_new + branch * kn_bstride + h * kn_hstride) + c * 16;
+            char* dst = reinterpret_cast<char*>(is_v ? tail_v : tail_k) + (row0 + t) * (D * 2) + c * 16;
+            *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
+        }
+        __syncthreads();  // (workgroup-scope release/acquire: the row is visible to the loads of this block below)
+        kbase = reinterpret_cast<const char*>(tail_k) + row0 * C::ROW_BYTES;
+        vbase = reinterpret_cast<const char*>(tail_v) + row0 * C::ROW_BYTES;
+        len = t + 1; c0 = 0; c1 = len;
+        slot0 = ((int64_t)branch * Hkv + h) * GT * FK_RT;
+        po = tail_o; pml = tail_ml;
+    } else {
+        auto len_of = [&](int hh) -> int { return (host_meta ? hm.len[hh] : k_len[hh]) + k_len_offset; };
+        int total = 0;
+        for (int hh = 0; hh < Hkv; ++hh) total += len_of(hh);
+        const int chunk = chunk_of(total, target_items);
+        int split = 0, first_item = 0;
+        h = -1;
+        {
+            int bx = (int)blockIdx.x - n_tail, items = 0;
+            for (int hh = 0; hh < Hkv; ++hh) {
+                const int n = max(1, (len_of(hh) + chunk - 1) / chunk);  // (an empty head still gets one item: it writes zeros)
+                if (h < 0) {
+                    if (bx < n) { h = hh; split = bx; first_item = items; }
+                    else bx -= n;
+                }
+                items += n;
+            }
+        }
+        if (h < 0) return;  // beyond the last item
+        if ((int)blockIdx.y * NT >= n_rtiles) return;
+        len = len_of(h);
+        const int64_t seg = host_meta ? hm.start[h] : k_start[h];
+        c0 = split * chunk;
+        c1 = min(len, c0 + chunk);
+        kbase = reinterpret_cast<const char*>(k) + seg * C::ROW_BYTES;
+        vbase = reinterpret_cast<const char*>(v) + seg * C::ROW_BYTES;
+        slot0 = ((int64_t)(first_item + split) * n_rtiles + (int64_t)blockIdx.y * NT) * FK_RT;
+        po = part_o; pml = part_ml;
+    }
+
+    __shared__ __attribute__((aligned(16))) char lds[FK_WAVES * C::WAVE_LDS];
+    char* wl = lds + wave * C::WAVE_LDS;
+    const float sl2 = scale * 1.44269504088896340736f;  // work in the exp2 domain
+
+    {
+        // ---- stationary Q fragments, one per row tile (B operand of S^T = K.Q^T): col = query row, k = head-dim slice ----
+        v8 qf[NT][C::KK];
+        int rows_valid[NT];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            int bq, gq, nrows;
+            if (branch >= 0) {
+                const int gt = grp * NT + i;
+                bq = branch; gq = gt * FK_RT + l15;
+                nrows = G - gt * FK_RT;
+            } else {
+                const int rt = (int)blockIdx.y * NT + i;
+                const int r = rt * FK_RT + l15;
+                bq = r / G; gq = r - bq * G;
+                nrows = R - rt * FK_RT;
+            }
+            rows_valid[i] = max(0, min(FK_RT, nrows));
+            const bool qvalid = l15 < rows_valid[i];
+            const T* qp = q + (qvalid ? (((int64_t)bq * Hkv + h) * G + gq) * D : 0) + quad * 8;
+#pragma unroll
+            for (int kk = 0; kk < C::KK; ++kk) {
+                u32x4 raw = *reinterpret_cast<const u32x4*>(qp + kk * 32);
+                if (!qvalid) raw = u32x4{0, 0, 0, 0};
+                qf[i][kk] = __builtin_bit_cast(v8, raw);
+            }
+        }
+        float m_run[NT], l_run[NT];
+        f4 o[NT][C::DB];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            m_run[i] = -INFINITY; l_run[i] = 0.f;
+#pragma unroll
+            for (int db = 0; db < C::DB; ++db) o[i][db] = f4{0.f, 0.f, 0.f, 0.f};
+        }
+
+        auto load_k = [&](u32x4 (&kr)[2][C::KK], int t0) {
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+                int key = t0 + sub * 16 + l15;
+                key = key < len ? key : len - 1;  // clamp (masked below)
+                const char* kp = kbase + (int64_t)key * C::ROW_BYTES + quad * 16;
+#pragma unroll
+                for (int kk = 0; kk < C::KK; ++kk) kr[sub][kk] = *reinterpret_cast<const u32x4*>(kp + kk * 64);
+            }
+        };
+        auto load_v = [&](u32x4 (&vr)[C::VLOADS], int t0) {
+#pragma unroll
+            for (int it = 0; it < C::VLOADS; ++it) {
+                const int c = it * WAVE + lane;
+                int key = t0 + c / C::CPR;
+                key = key < len ? key : len - 1;
+                vr[it] = *reinterpret_cast<const u32x4*>(vbase + (int64_t)key * C::ROW_BYTES + (c % C::CPR) * 16);
+            }
+        };
+        // Two row tiles at head dim 128 leave no registers for a second K and V buffer (with them 51 registers spilled to scratch): there
+        // the next tile's V rows are requested into the SAME registers right after the current ones have gone to LDS, and its K rows
+        // right after the S^T products have consumed the current ones - still unconditionally, and in flight during the softmax and
+        // the P.V products of the current tile.
+        constexpr bool VLATE = NT * D > 128;
+        u32x4 kraw[2][C::KK], vraw[C::VLOADS], knext[VLATE ? 1 : 2][C::KK], vnext[VLATE ? 1 : C::VLOADS];
+        // one 32-key tile of this wave, applied to the NT row tiles: the K fragments feed NT S^T = K.Q^T products, the V tile goes
+        // through the wave's LDS tile once and every transposed fragment read back from it feeds NT O^T += V^T.P^T products
+        auto compute_tile = [&](u32x4 (&kr)[2][C::KK], u32x4 (&vr)[C::VLOADS], int t0, int t_next, auto refill) __attribute__((always_inline)) {
+#pragma unroll
+            for (int it = 0; it < C::VLOADS; ++it) {
+                const int c = it * WAVE + lane;
+                *reinterpret_cast<u32x4*>(wl + (c / C::CPR) * C::VSTRIDE + (c % C::CPR) * 16) = vr[it];
+            }
+            if constexpr (decltype(refill)::value) load_v(vr, t_next);
+            f4 s[NT][2];
+#pragma unroll
+            for (int i = 0; i < NT; ++i)
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    s[i][sub] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int kk = 0; kk < C::KK; ++kk)
+                        s[i][sub] = Half<T>::mfma(__builtin_bit_cast(v8, kr[sub][kk]), qf[i][kk], s[i][sub]);
+                }
+            if constexpr (decltype(refill)::value) load_k(kr, t_next);  // (the K fragments are spent: the next tile's take their registers)
+            v8 pb[NT];
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                float sv[8];
+                float tmax = -INFINITY;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int key = t0 + (j >> 2) * 16 + quad * 4 + (j & 3);
+                    float x = s[i][j >> 2][j & 3] * sl2;
+                    x = key < c1 ? x : -INFINITY;
+                    sv[j] = x;
+                    tmax = fmaxf(tmax, x);
+                }
+                tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+                tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+                const float m_new = fmaxf(m_run[i], tmax);
+                const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
+                const float alpha = exp2f(m_run[i] - m_safe);
+                float psum = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float p = exp2f(sv[j] - m_safe);
+                    psum += p;
+                    pb[i][j] = (T)p;
+                }
+                l_run[i] = l_run[i] * alpha + psum;
+                m_run[i] = m_new;
+#pragma unroll
+                for (int db = 0; db < C::DB; ++db) {
+                    o[i][db][0] *= alpha; o[i][db][1] *= alpha; o[i][db][2] *= alpha; o[i][db][3] *= alpha;
+                }
+            }
+            const char* trp = wl + (quad * 4 + (l15 >> 2)) * C::VSTRIDE + (l15 & 3) * 8;
+#pragma unroll
+            for (int db = 0; db < C::DB; ++db) {
+                s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(trp + db * 32));
+                s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(trp + 16 * C::VSTRIDE + db * 32));
+                s8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+                for (int i = 0; i < NT; ++i) o[i][db] = Half<T>::mfma(__builtin_bit_cast(v8, both), pb[i], o[i][db]);
+            }
+        };
+        // The wave's tiles, one requested AHEAD of the one being computed; the steady-state loop issues the next tile's loads
+        // UNCONDITIONALLY and the last tile is computed after the loop (the load structure of varlen_attn_split2_kernel: its comment
+        // records what the conditional form cost).
+        const int t_first = c0 + wave * FK_KT;
+        constexpr int T_STEP = FK_WAVES * FK_KT;
+        if (t_first < c1) {
+            load_k(kraw, t_first);
+            load_v(vraw, t_first);
+            int t0 = t_first;
+#pragma unroll 1
+            for (; t0 + T_STEP < c1; t0 += T_STEP) {
+                if constexpr (!VLATE) {
+                    load_k(knext, t0 + T_STEP);
+                    load_v(vnext, t0 + T_STEP);
+                }
+                compute_tile(kraw, vraw, t0, t0 + T_STEP, std::integral_constant<bool, VLATE>{});
+                if constexpr (!VLATE) {
+#pragma unroll
+                    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+                        for (int kk = 0; kk < C::KK; ++kk) kraw[sub][kk] = knext[sub][kk];
+#pragma unroll
+                    for (int it = 0; it < C::VLOADS; ++it) vraw[it] = vnext[it];
+                }
+            }
+            compute_tile(kraw, vraw, t0, 0, std::false_type{});
+        }
+
+        // ---- merge the 8 waves of the block through LDS, one row tile after the other (each wave stages in its own V tile) ----
+        constexpr int WSTR = D + 4;                          // floats per staged row (bank-conflict-free, see kvz_attn.hip)
+        static_assert((FK_RT * WSTR + 2 * FK_RT) * 4 <= C::WAVE_LDS, "the wave's V tile holds its merge staging");
+        float* wo = reinterpret_cast<float*>(wl);            // [16 q][D + 4]
+        float* wm = wo + FK_RT * WSTR;                       // [16] m, [16] l
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            float lr = l_run[i];
+            lr += __shfl_xor(lr, 16, 64);
+            lr += __shfl_xor(lr, 32, 64);
+            const int rv = rows_valid[i];
+            if (l15 < rv) {
+#pragma unroll
+                for (int db = 0; db < C::DB; ++db) *reinterpret_cast<f4*>(wo + l15 * WSTR + db * 16 + quad * 4) = o[i][db];
+                if (quad == 0) { wm[l15] = m_run[i]; wm[16 + l15] = lr; }
+            }
+            __syncthreads();
+            const int64_t pbase = slot0 + (int64_t)(grp * NT + i) * FK_RT;
+            for (int e = threadIdx.x; e < rv * (D / 4); e += FK_THREADS) {
+                const int qq = e / (D / 4), d = (e % (D / 4)) * 4;
+                float mw[FK_WAVES], M = -INFINITY;
+#pragma unroll
+                for (int w = 0; w < FK_WAVES; ++w) {
+                    mw[w] = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS)[FK_RT * WSTR + qq];
+                    M = fmaxf(M, mw[w]);
+                }
+                f4 acc4 = f4{0.f, 0.f, 0.f, 0.f};
+                float lsum = 0.f;
+#pragma unroll
+                for (int w = 0; w < FK_WAVES; ++w) {
+                    const float* pw = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS);
+                    const float wgt = (mw[w] == -INFINITY) ? 0.f : exp2f(mw[w] - M);
+                    const f4 ov = *reinterpret_cast<const f4*>(pw + qq * WSTR + d);
+                    acc4[0] += wgt * ov[0]; acc4[1] += wgt * ov[1]; acc4[2] += wgt * ov[2]; acc4[3] += wgt * ov[3];
+                    lsum += wgt * pw[FK_RT * WSTR + 16 + qq];
+                }
+                *reinterpret_cast<f4*>(po + (pbase + qq) * D + d) = acc4;
+                if (d == 0) *reinterpret_cast<float2*>(pml + (pbase + qq) * 2) = make_float2(M, lsum);
+            }
+            __syncthreads();  // (the staging of this row tile has been read: the next one - or the next group's V tiles - may overwrite it)
+        }
+    }
+}
+
+// merge, per (head, branch, group row), the partials of the head's key ranges and of the branch's tail.  grid = (Hkv, B, G);
+// block = 1024 threads = (1024/D) slices of the partials x D columns.  out = (T)(a / l).
+constexpr int CB_THREADS = 1024;
+template <typename T, int D>
+__global__ __launch_bounds__(CB_THREADS) void fork_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                                                 const float* __restrict__ tail_o, const float* __restrict__ tail_ml,
+                                                                 const int32_t* __restrict__ k_len, int k_len_offset, HeadMeta hm,
+                                                                 int host_meta, TailLens tl, int B, int Hkv, int G, int target_items,
+                                                                 int n_rtiles, T* __restrict__ out) {
+    constexpr int SLICES = CB_THREADS / D;
+    const int h = blockIdx.x, b = blockIdx.y, g = blockIdx.z;
+    const int tid = threadIdx.x;
+    const int d = tid % D, slice = tid / D;
+    const int64_t orow = (((int64_t)b * Hkv + h) * G + g) * D;
+    if (tl.n[b] < 0) {  // inactive branch
+        if (tid < D) out[orow + tid] = (T)0.f;
+        return;
+    }
+    auto len_of = [&](int hh) -> int { return (host_meta ? hm.len[hh] : k_len[hh]) + k_len_offset; };
+    int total = 0;
+    for (int hh = 0; hh < Hkv; ++hh) total += len_of(hh);
+    const int chunk = chunk_of(total, target_items);
+    int first_item = 0;
+    for (int hh = 0; hh < h; ++hh) first_item += max(1, (len_of(hh) + chunk - 1) / chunk);
+    const int nsp = max(1, (len_of(h) + chunk - 1) / chunk);
+    const int r = b * G + g;
+    const int64_t base = ((int64_t)first_item * n_rtiles + r / FK_RT) * FK_RT + r % FK_RT;
+    const int64_t istride = (int64_t)n_rtiles * FK_RT;
+    const int GT = (G + FK_RT - 1) / FK_RT;
+    const int64_t trow = (((int64_t)b * Hkv + h) * GT + g / FK_RT) * FK_RT + g % FK_RT;
+    const int n = nsp + 1;  // the key ranges of the head, then the branch's tail (an active branch has at least its new row)
+    auto ml_ptr = [&](int s2) -> const float* { return s2 < nsp ? part_ml + (base + s2 * istride) * 2 : tail_ml + trow * 2; };
+    auto o_ptr = [&](int s2) -> const float* { return s2 < nsp ? part_o + (base + s2 * istride) * D : tail_o + trow * D; };
+
+    __shared__ float s_red[CB_THREADS / WAVE];
+    __shared__ float s_acc[SLICES][D];
+    __shared__ float s_l[SLICES];
+
+    constexpr int PER = 8;  // partials per thread on the fast path
+    float acc = 0.f, lp = 0.f;
+    if (n <= PER * SLICES) {
+        // ONE round trip to memory: every thread issues the loads of its (up to 8) partials before anything depends on them
+        float2 ml[PER];
+        float ov[PER];
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int s2 = slice + i * SLICES;
+            const int sc = min(s2, n - 1);
+            ml[i] = *reinterpret_cast<const float2*>(ml_ptr(sc));
+            ov[i] = o_ptr(sc)[d];
+            if (s2 >= n) ml[i] = make_float2(-INFINITY, 0.f);
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) mx = fmaxf(mx, ml[i].x);
+        mx = wave_reduce_max(mx);
+        if ((tid & 63) == 0) s_red[tid >> 6] = mx;
+        __syncthreads();
+        float M = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < CB_THREADS / WAVE; ++w) M = fmaxf(M, s_red[w]);
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const float wgt = (ml[i].x == -INFINITY) ? 0.f : exp2f(ml[i].x - M);
+            acc += wgt * ov[i];
+            lp += wgt * ml[i].y;
+        }
+    } else {
+        // more partials than the fast path holds in registers: the maximum first, then one pass over the partials
+        float mx = -INFINITY;
+        for (int s2 = tid; s2 < n; s2 += CB_THREADS) mx = fmaxf(mx, ml_ptr(s2)[0]);
+        mx = wave_reduce_max(mx);
+        if ((tid & 63) == 0) s_red[tid >> 6] = mx;
+        __syncthreads();
+        float M = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < CB_THREADS / WAVE; ++w) M = fmaxf(M, s_red[w]);
+        for (int s2 = slice; s2 < n; s2 += SLICES) {
+            const float2 ml = *reinterpret_cast<const float2*>(ml_ptr(s2));
+            const float wgt = (ml.x == -INFINITY) ? 0.f : exp2f(ml.x - M);
+            acc += wgt * o_ptr(s2)[d];
+            lp += wgt * ml.y;
+        }
+    }
+    s_acc[slice][d] = acc;
+    if (d == 0) s_l[slice] = lp;  // (every column of a slice holds the same share of the denominator)
+    __syncthreads();
+    if (tid < D) {
+        float a = 0.f, l = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < SLICES; ++sl) { a += s_acc[sl][tid]; l += s_l[sl]; }
+        out[orow + tid] = (T)((l > 0.f) ? a / l : 0.f);
+    }
+}
+
+// out[r, :] = merge of (o1[r, :], lse1[r]) and (o2[r, :], lse2[r]); one thread per 8 elements (16 bytes)
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_merge_lse_kernel(const T* o1, const float* __restrict__ lse1, const T* o2,
+                                                            const float* __restrict__ lse2, T* out, int64_t rows) {
+    typedef typename Half<T>::v8 v8;
+    constexpr int CPR = D / 8;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * CPR) return;
+    const int64_t r = i / CPR;
+    const float a = lse1[r], b = lse2[r];
+    const float m = fmaxf(a, b);
+    float w1 = 0.f, w2 = 0.f;
+    if (m != -INFINITY) { w1 = expf(a - m); w2 = expf(b - m); }
+    const float den = w1 + w2;
+    const v8 x = *reinterpret_cast<const v8*>(o1 + i * 8);
+    const v8 y = *reinterpret_cast<const v8*>(o2 + i * 8);
+    v8 z;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        // (a weight of 0 must silence its side whatever that side holds: rows without a key are not written by every kernel)
+        const float xs = w1 > 0.f ? w1 * (float)x[j] : 0.f;
+        const float ys = w2 > 0.f ? w2 * (float)y[j] : 0.f;
+        z[j] = (T)(den > 0.f ? (xs + ys) / den : 0.f);
+    }
+    *reinterpret_cast<v8*>(out + i * 8) = z;
+}
+
+// work items of the shared part: the decode kernel's count (one block per CU) less the tail items of the same launch
+static inline int fork_items(int B, int Hkv) {
+    int t = tunable(TUNE_ATTN_ITEMS);
+    if (t <= 0) {
+        const int cus = device_cus();
+        t = Hkv < cus * 3 / 4 ? cus - Hkv : cus / 4;
+    }
+    const int floor_items = device_cus() / 4;
+    return t - B * Hkv > floor_items ? t - B * Hkv : (t < floor_items ? t : floor_items);
+}
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct ForkWs { float* part_ml; float* part_o; float* tail_ml; float* tail_o; size_t bytes; };
+static inline ForkWs fork_ws(void* ws, int B, int Hkv, int G, int D) {
+    const int n_rtiles = (B * G + FK_RT - 1) / FK_RT;
+    const int GT = (G + FK_RT - 1) / FK_RT;
+    // (sized for the largest item count any B gives: a workspace made once serves every wave of branches)
+    int t = tunable(TUNE_ATTN_ITEMS);
+    if (t <= 0) t = device_cus();
+    const size_t items = (size_t)t + Hkv;
+    const size_t trows = (size_t)B * Hkv * GT * FK_RT;
+    ForkWs w;
+    char* p = reinterpret_cast<char*>(ws);
+    w.part_ml = reinterpret_cast<float*>(p);
+    p += align256(items * n_rtiles * FK_RT * 2 * sizeof(float));
+    w.part_o = reinterpret_cast<float*>(p);
+    p += align256(items * n_rtiles * FK_RT * D * sizeof(float));
+    w.tail_ml = reinterpret_cast<float*>(p);
+    p += align256(trows * 2 * sizeof(float));
+    w.tail_o = reinterpret_cast<float*>(p);
+    p += align256(trows * D * sizeof(float));
+    w.bytes = (size_t)(p - reinterpret_cast<char*>(ws));
+    return w;
+}
+
+template <typename T, int D, int NT>
+static void launch_fork_nt(dim3 grid, hipStream_t stream, const void* q, const void* k, const void* v, const int32_t* k_start,
+                           const int32_t* k_len, int k_len_offset, const HeadMeta& hm, int host, void* tail_k, void* tail_v, int tail_cap,
+                           const TailLens& tl, const void* k_new, const void* v_new, int64_t kn_b, int64_t kn_h, int64_t vn_b, int64_t vn_h,
+                           int B, int Hkv, int G, int target, float scale, const ForkWs& w, int n_rtiles) {
+    hipLaunchKernelGGL((fork_attn_kernel<T, D, NT>), grid, dim3(FK_THREADS), 0, stream, reinterpret_cast<const T*>(q),
+                       reinterpret_cast<const T*>(k), reinterpret_cast<const T*>(v), k_start, k_len, k_len_offset, hm, host,
+                       reinterpret_cast<T*>(tail_k), reinterpret_cast<T*>(tail_v), tail_cap, tl, reinterpret_cast<const T*>(k_new),
+                       reinterpret_cast<const T*>(v_new), kn_b, kn_h, vn_b, vn_h, B, Hkv, G, target, scale, w.part_o, w.part_ml, w.tail_o,
+                       w.tail_ml, n_rtiles);
+}
+
+template <typename T, int D>
+static int launch_fork(const void* q, const void* k, const void* v, const int32_t* k_start, const int32_t* k_len, int k_len_offset,
+                       const int32_t* meta_host, void* tail_k, void* tail_v, int tail_cap, const int32_t* tail_len, const void* k_new,
+                       const void* v_new, int64_t kn_b, int64_t kn_h, int64_t vn_b, int64_t vn_h, int B, int Hkv, int G, float scale,
+                       void* out, void* ws, hipStream_t stream) {
+    const int n_rtiles = (B * G + FK_RT - 1) / FK_RT;
+    const ForkWs w = fork_ws(ws, B, Hkv, G, D);
+    HeadMeta hm;
+    const int host = meta_host != nullptr;
+    for (int h = 0; h < FK_MAXH; ++h) {
+        hm.start[h] = host && h < Hkv ? meta_host[h] : 0;
+        hm.len[h] = host && h < Hkv ? meta_host[Hkv + h] : 0;
+    }
+    TailLens tl;
+    for (int b = 0; b < FK_MAXB; ++b) tl.n[b] = b < B ? tail_len[b] : -1;
+    ProfScope ps("fork_attn", stream);
+    // two row tiles per block from two row tiles on; three or four row tiles are two blocks per work item (grid.y)
+    const int nt = n_rtiles >= 2 ? 2 : 1;
+    const int GT = (G + FK_RT - 1) / FK_RT, TG = (GT + nt - 1) / nt;
+    const int target = fork_items(B * TG, Hkv);
+    const dim3 grid(B * Hkv * TG + target + Hkv, (n_rtiles + nt - 1) / nt);
+    if (nt == 2)
+        launch_fork_nt<T, D, 2>(grid, stream, q, k, v, k_start, k_len, k_len_offset, hm, host, tail_k, tail_v, tail_cap, tl, k_new, v_new,
+                                kn_b, kn_h, vn_b, vn_h, B, Hkv, G, target, scale, w, n_rtiles);
+    else
+        launch_fork_nt<T, D, 1>(grid, stream, q, k, v, k_start, k_len, k_len_offset, hm, host, tail_k, tail_v, tail_cap, tl, k_new, v_new,
+                                kn_b, kn_h, vn_b, vn_h, B, Hkv, G, target, scale, w, n_rtiles);
+    KVZ_CHECK_LAUNCH("fork_attn_kernel");
+    hipLaunchKernelGGL((fork_combine_kernel<T, D>), dim3(Hkv, B, G), dim3(CB_THREADS), 0, stream, w.part_o, w.part_ml, w.tail_o,
+                       w.tail_ml, k_len, k_len_offset, hm, host, tl, B, Hkv, G, target, n_rtiles, reinterpret_cast<T*>(out));
+    KVZ_CHECK_LAUNCH("fork_combine_kernel");
+    return KVZ_OK;
+}
+
+}  // namespace fork
+}  // namespace kvz
+
+using namespace kvz;
+
+extern "C" size_t kvz_fork_attn_workspace_bytes(int B, int Hkv, int G, int D, int max_len_k) {
+    if (B <= 0 || Hkv <= 0 || G <= 0 || D <= 0 || max_len_k < 0) return 0;
+    return fork::fork_ws(nullptr, B, Hkv, G, D).bytes;
+}
+
+extern "C" int kvz_fork_attn_append(const void* q, const void* k_cache, const void* v_cache, const int32_t* k_start,
+                                    const int32_t* k_len, int k_len_offset, const int32_t* k_meta_host, void* tail_k, void* tail_v,
+                                    int tail_cap, const int32_t* tail_len_host, const void* k_new, const void* v_new,
+                                    int64_t k_new_batch_stride, int64_t k_new_head_stride, int64_t v_new_batch_stride,
+                                    int64_t v_new_head_stride, int B, int Hkv, int G, int D, float scale, int dtype, void* out, void* ws,
+                                    size_t ws_bytes, kvz_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    KVZ_REQUIRE(q && k_cache && v_cache && tail_k && tail_v && tail_len_host && k_new && v_new && out && ws
+                    && ((k_start && k_len) || k_meta_host), KVZ_EINVAL, "kvz_fork_attn_append: null pointer");
+    KVZ_REQUIRE(B > 0 && Hkv > 0 && G > 0 && tail_cap > 0 && k_len_offset >= 0, KVZ_EINVAL, "kvz_fork_attn_append: bad shape");
+    KVZ_REQUIRE(D == 64 || D == 128, KVZ_EUNSUPPORTED, "kvz_fork_attn_append: head_dim %d unsupported (64 or 128)", D);
+    KVZ_REQUIRE((int64_t)B * G <= fork::FK_MAXROWS && B <= fork::FK_MAXB, KVZ_EUNSUPPORTED,
+                "kvz_fork_attn_append: %d branches x %d query heads per KV head unsupported (B*G <= %d query rows per head, B <= %d)", B, G,
+                fork::FK_MAXROWS, fork::FK_MAXB);
+    KVZ_REQUIRE(Hkv <= fork::FK_MAXH, KVZ_EUNSUPPORTED, "kvz_fork_attn_append: %d KV heads unsupported (<= %d)", Hkv, fork::FK_MAXH);
+    KVZ_REQUIRE(dtype == KVZ_F16 || dtype == KVZ_BF16, KVZ_EINVAL, "kvz_fork_attn_append: bad dtype %d", dtype);
+    KVZ_REQUIRE(aligned16(q) && aligned16(k_cache) && aligned16(v_cache) && aligned16(tail_k) && aligned16(tail_v) && aligned16(k_new)
+                    && aligned16(v_new) && aligned16(out) && aligned16(ws), KVZ_EINVAL,
+                "kvz_fork_attn_append: pointers must be 16-byte aligned");
+    KVZ_REQUIRE(k_new_batch_stride % 8 == 0 && k_new_head_stride % 8 == 0 && v_new_batch_stride % 8 == 0 && v_new_head_stride % 8 == 0,
+                KVZ_EINVAL, "kvz_fork_attn_append: the strides of the new rows must be multiples of 8 elements");
+    for (int b = 0; b < B; ++b)
+        KVZ_REQUIRE(tail_len_host[b] >= -1 && tail_len_host[b] < tail_cap, KVZ_EINVAL,
+                    "kvz_fork_attn_append: tail_len[%d] = %d outside [-1, tail_cap = %d): the new row does not fit", b, tail_len_host[b],
+                    tail_cap);
+    if (k_meta_host)
+        for (int h = 0; h < Hkv; ++h)
+            KVZ_REQUIRE(k_meta_host[h] >= 0 && k_meta_host[Hkv + h] + k_len_offset >= 0, KVZ_EINVAL,
+                        "kvz_fork_attn_append: negative segment start or length of head %d", h);
+    KVZ_REQUIRE(ws_bytes >= kvz_fork_attn_workspace_bytes(B, Hkv, G, D, 0), KVZ_EWORKSPACE, "kvz_fork_attn_append: workspace too small");
+#define KVZ_FORK_ARGS q, k_cache, v_cache, k_start, k_len, k_len_offset, k_meta_host, tail_k, tail_v, tail_cap, tail_len_host, k_new, v_new, \
+                      k_new_batch_stride, k_new_head_stride, v_new_batch_stride, v_new_head_stride, B, Hkv, G, scale, out, ws, stream
+    if (dtype == KVZ_F16) {
+        if (D == 128) return fork::launch_fork<_Float16, 128>(KVZ_FORK_ARGS);
+        return fork::launch_fork<_Float16, 64>(KVZ_FORK_ARGS);
+    }
+    if (D == 128) return fork::launch_fork<__bf16, 128>(KVZ_FORK_ARGS);
+    return fork::launch_fork<__bf16, 64>(KVZ_FORK_ARGS);
+#undef KVZ_FORK_ARGS
+}
+
+extern "C" int kvz_attn_merge_lse(const void* o1, const float* lse1, const void* o2, const float* lse2, void* out, int64_t rows, int D,
+                                  int dtype, kvz_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    KVZ_REQUIRE(o1 && lse1 && o2 && lse2 && out, KVZ_EINVAL, "kvz_attn_merge_lse: null pointer");
+    KVZ_REQUIRE(rows >= 0 && rows < ((int64_t)1 << 40), KVZ_EINVAL, "kvz_attn_merge_lse: bad shape");
+    KVZ_REQUIRE(D == 64 || D == 128, KVZ_EUNSUPPORTED, "kvz_attn_merge_lse: head_dim %d unsupported (64 or 128)", D);
+    KVZ_REQUIRE(dtype == KVZ_F16 || dtype == KVZ_BF16, KVZ_EINVAL, "kvz_attn_merge_lse: bad dtype %d", dtype);
+    KVZ_REQUIRE(aligned16(o1) && aligned16(o2) && aligned16(out), KVZ_EINVAL, "kvz_attn_merge_lse: pointers must be 16-byte aligned");
+    if (rows == 0) return KVZ_OK;
+    const int64_t n = rows * (D / 8);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+#define KVZ_MERGE_LAUNCH(T, DD)                                                                                                       \
+    hipLaunchKernelGGL((fork::attn_merge_lse_kernel<T, DD>), grid, block, 0, stream, reinterpret_cast<const T*>(o1), lse1,              \
+                       reinterpret_cast<const T*>(o2), lse2, reinterpret_cast<T*>(out), rows)
+    if (dtype == KVZ_F16) { if (D == 128) KVZ_MERGE_LAUNCH(_Float16, 128); else KVZ_MERGE_LAUNCH(_Float16, 64); }
+    else { if (D == 128) KVZ_MERGE_LAUNCH(__bf16, 128); else KVZ_MERGE_LAUNCH(__bf16, 64); }
+#undef KVZ_MERGE_LAUNCH
+    KVZ_CHECK_LAUNCH("attn_merge_lse_kernel");
+    return KVZ_OK;
+}

@@ -476,6 +476,11 @@ class EvictCache(_CacheBase):
         self.info["offset"][layer_idx] = off + 1
         return out
 
+    def fork(self, n_branches: int, tail_capacity: int = 256) -> "ForkedCache":
+        """``n_branches`` concurrent queries over this pruned cache: the branches share its rows read-only and each owns a private
+        tail for the K,V of its query and of its answer (see ``ForkedCache``)."""
+        return ForkedCache(self, n_branches, tail_capacity=tail_capacity)
+
     # ---- a whole generation step as ONE HIP graph ---------------------------------------------------------------------------
     def decode_graph(self, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, softmax_scale: Optional[float] = None):
         """Capture the attention part of ONE generation step over all layers - L x (append the token's K,V + variable-length
@@ -545,6 +550,144 @@ class DecodeGraph:
         kv._seen_tokens += 1
         kv._dyn_val += 1
         return self.out
+
+
+class ForkedCache:
+    """``n_branches`` concurrent queries over ONE pruned slack-layout ``EvictCache`` (``EvictCache.fork``; no reference counterpart:
+    batch is 1 there).  The branches share the base cache's flat K,V read-only - its rows, segment starts and lengths as they were at
+    the fork, rows a multi-turn ``update_cache=True`` appended before it included - and every branch owns a private tail per layer
+    (``[B, Hkv, tail_capacity, D]``: the K,V of its query tokens and of the tokens it generates).  One decode step of all live
+    branches is one attention launch per layer that reads the shared rows once (``kvz_fork_attn_append``).
+
+    Hooks for the attention adapter (``kvzip_amd.attn``):
+      * ``first_step`` - the query of ONE branch (``select_branch`` names it), ``q_len > 1``: ``kvz_flash_fwd`` over the shared
+        segments (no mask) and over the branch's tail (causal), merged by their LSEs;
+      * ``update_attend`` - ``[B, H, 1, D]`` queries, one new token per live branch.
+    The fork never changes ``info["offset"]``, ``_seen_tokens`` or any row of the base cache.  A prune or a slack growth of the base
+    moves the rows the fork points at: every hook then raises ``KvzError`` (as ``DecodeGraph.replay`` does)."""
+
+    def __init__(self, base: "EvictCache", n_branches: int, tail_capacity: int = 256):
+        if not (isinstance(base, EvictCache) and base.pruned and base.info.get("flatten") and base.layout == "slack"):
+            raise ops.KvzError("fork: needs a pruned EvictCache in the slack layout")
+        G = base.n_group_kv
+        if n_branches < 1 or n_branches > ops.FORK_MAX_BRANCHES or n_branches * G > ops.FORK_MAX_ROWS:
+            raise ops.KvzError(f"fork: {n_branches} branches x {G} query heads per KV head: one launch takes at most "
+                               f"{ops.FORK_MAX_ROWS} query rows per KV head and {ops.FORK_MAX_BRANCHES} branches")
+        if base.n_heads_kv > 64:
+            raise ops.KvzError("fork: more than 64 KV heads")
+        offs = base.info["offset"]
+        self.base, self.n_branches = base, int(n_branches)
+        self.n_layers, self.n_heads_kv, self.n_group_kv = base.n_layers, base.n_heads_kv, G
+        self.device, self.dtype = base.device, base.dtype
+        self.pruned, self.get_score, self.layout = True, False, "fork"
+        self._epoch = base._layout_epoch
+        self._offset = list(offs)                                   # rows appended to the base before the fork, per layer
+        self._k = list(base.key_cache)                              # references: the storage outlives a re-layout of the base
+        self._v = list(base.value_cache)
+        self._seg = list(base.info["seg_start"])
+        self._len = list(base.info["len_k"])
+        self._meta = list(base.info["meta_host"])
+        seg = [list(m[:self.n_heads_kv]) for m in self._meta]
+        self._starts = seg
+        self._lens = [[n + self._offset[l] for n in base.info["len_k_host"][l]] for l in range(self.n_layers)]
+        self.tail_capacity = max(int(tail_capacity), 1)
+        self.tail_k: List[Optional[torch.Tensor]] = [None] * self.n_layers   # allocated at a layer's first use (the head dim is the call's)
+        self.tail_v: List[Optional[torch.Tensor]] = [None] * self.n_layers
+        self.tail_len = [[0] * self.n_branches for _ in range(self.n_layers)]
+        self.active = [True] * self.n_branches
+        self._branch = 0
+        self._ws = None
+
+    # -- bookkeeping ---------------------------------------------------------------------------------
+    def get_seq_length(self, layer_idx: Optional[int] = 0) -> int:
+        return self.base.get_seq_length(layer_idx)
+
+    def select_branch(self, b: int) -> None:
+        """The branch the next ``first_step`` calls belong to."""
+        assert 0 <= b < self.n_branches
+        self._branch = int(b)
+
+    def retire(self, b: int) -> None:
+        """Branch ``b`` is finished (EOS, token budget): later decode steps skip it (no write, zero output rows)."""
+        self.active[b] = False
+
+    def _check(self, layer_idx: int) -> None:
+        base = self.base
+        if self._epoch != base._layout_epoch or not base.info.get("flatten"):
+            raise ops.KvzError("forked cache: the base cache was re-laid out since the fork (prune / slack growth): fork again")
+        if base.info["offset"][layer_idx] < self._offset[layer_idx]:
+            raise ops.KvzError("forked cache: the base cache was sliced below the rows it held at the fork: fork again")
+
+    def _tails(self, layer_idx: int, need: int, D: int):
+        """The layer's tails with room for ``need`` rows per branch (re-allocated with at least twice the capacity when outgrown)."""
+        tk = self.tail_k[layer_idx]
+        if tk is None or tk.shape[2] < need:
+            cap = self.tail_capacity if tk is None else tk.shape[2]
+            while cap < need:
+                cap *= 2
+            shape = (self.n_branches, self.n_heads_kv, cap, D)
+            nk = torch.empty(shape, dtype=self.dtype, device=self.device)
+            nv = torch.empty(shape, dtype=self.dtype, device=self.device)
+            if tk is not None:
+                nk[:, :, :tk.shape[2]].copy_(tk)
+                nv[:, :, :tk.shape[2]].copy_(self.tail_v[layer_idx])
+            self.tail_k[layer_idx], self.tail_v[layer_idx] = nk, nv
+            self.tail_capacity = max(self.tail_capacity, cap)
+        return self.tail_k[layer_idx], self.tail_v[layer_idx]
+
+    # -- hooks ------------------------------------------------------------------------------------------
+    def first_step(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
+                   softmax_scale: Optional[float] = None) -> torch.Tensor:
+        """The query of the selected branch: query ``[1, H, q, D]``, key / value ``[1, Hkv, q, D]``.  Appends the K,V rows to the
+        branch's tail and returns the attention over shared segment ++ tail (bottom-right causal inside the tail) as
+        ``[Hkv, q, G, D]``."""
+        self._check(layer_idx)
+        b = self._branch
+        bsz, _, q_len, D = query_states.shape
+        if bsz != 1:
+            raise ops.KvzError("forked cache: the first step of a branch runs at batch 1")
+        Hkv = self.n_heads_kv
+        t = self.tail_len[layer_idx][b]
+        tk, tv = self._tails(layer_idx, t + q_len, D)
+        cap = tk.shape[2]
+        if key_states.stride(-1) != 1 or value_states.stride(-1) != 1:
+            key_states, value_states = key_states.contiguous(), value_states.contiguous()
+        lib = ops._lib.load()
+        rc = lib.kvz_dense_append(tk[b].data_ptr(), tv[b].data_ptr(), cap * D, t, key_states.data_ptr(), value_states.data_ptr(),
+                                  key_states.stride(1), key_states.stride(2), value_states.stride(1), value_states.stride(2),
+                                  Hkv, q_len, D, tk.element_size(), ops._stream(tk))
+        ops.check(rc, "kvz_dense_append")
+        o1, l1 = ops.flash_fwd_ragged(query_states, self._k[layer_idx], self._v[layer_idx], self._starts[layer_idx],
+                                      self._lens[layer_idx], causal=False, softmax_scale=softmax_scale)
+        o2, l2 = ops.flash_fwd_ragged(query_states, tk[b].view(-1, D), tv[b].view(-1, D), [h * cap for h in range(Hkv)],
+                                      [t + q_len] * Hkv, causal=True, softmax_scale=softmax_scale)
+        self.tail_len[layer_idx][b] = t + q_len
+        return ops.attn_merge_lse(o1, l1, o2, l2, out=o1)
+
+    def update_attend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
+                      softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Decode step of all branches: query ``[B, H, 1, D]``, key / value ``[B, Hkv, 1, D]`` -> ``[B, Hkv, G, D]``.  Live branches
+        get their new row appended to their tail; retired ones are skipped (their output rows are zero)."""
+        self._check(layer_idx)
+        B, _, q_len, D = query_states.shape
+        if B != self.n_branches or q_len != 1:
+            raise ops.KvzError(f"forked cache: a decode step takes [{self.n_branches}, H, 1, D] queries (got batch {B}, {q_len} positions)")
+        lens = self.tail_len[layer_idx]
+        tk, tv = self._tails(layer_idx, max(lens) + 1, D)
+        if key_states.stride(-1) != 1 or value_states.stride(-1) != 1 or key_states.stride(0) % 8 or key_states.stride(1) % 8 \
+                or value_states.stride(0) % 8 or value_states.stride(1) % 8:
+            key_states, value_states = key_states.contiguous(), value_states.contiguous()
+        if self._ws is None or self._ws[0] != D:
+            self._ws = (D, ops.fork_attn_workspace(B, self.n_heads_kv, self.n_group_kv, D, self.device))
+        q = query_states.reshape(B, self.n_heads_kv, self.n_group_kv, D).contiguous()
+        tl = [n if a else -1 for n, a in zip(lens, self.active)]
+        out = ops.fork_attn_append(q, self._k[layer_idx], self._v[layer_idx], self._seg[layer_idx], self._len[layer_idx],
+                                   self._offset[layer_idx], tk, tv, tl, key_states, value_states, softmax_scale=softmax_scale,
+                                   workspace=self._ws[1], meta_host=self._meta[layer_idx], out=out)
+        for b in range(B):
+            if self.active[b]:
+                lens[b] += 1
+        return out
 
 
 class RetainCache(_CacheBase):

@@ -448,6 +448,101 @@ def flash_fwd(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, causa
     return out
 
 
+# --------------------------------------------------------------------------------------------------
+# forked decode: B queries over one shared pruned cache (no reference counterpart: batch is 1 there)
+# --------------------------------------------------------------------------------------------------
+FORK_MAX_ROWS = 64      # query rows (branches x query heads per KV head) of one forked decode launch
+FORK_MAX_BRANCHES = 16
+
+
+def fork_attn_workspace(B: int, Hkv: int, G: int, D: int, device) -> torch.Tensor:
+    """Scratch of ``fork_attn_append`` (partials of the shared key ranges and of the tails); no initialisation needed."""
+    need = _lib.load().kvz_fork_attn_workspace_bytes(B, Hkv, G, D, 0)
+    return torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+
+
+def fork_attn_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_start: Optional[torch.Tensor],
+                     k_len: Optional[torch.Tensor], k_len_offset: int, tail_k: torch.Tensor, tail_v: torch.Tensor,
+                     tail_len: Sequence[int], k_new: torch.Tensor, v_new: torch.Tensor, softmax_scale: Optional[float] = None,
+                     workspace: Optional[torch.Tensor] = None, meta_host=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One decode step of B branches over one shared flat cache (``kvz_fork_attn_append``).  q ``[B, Hkv, G, D]``; k_cache / v_cache
+    ``[rows, D]`` (read only; head h owns rows ``k_start[h] : + k_len[h] + k_len_offset``, device arrays and / or ``meta_host``);
+    tail_k / tail_v ``[B, Hkv, tail_cap, D]``; ``tail_len[b]`` rows in use (-1: inactive branch); k_new / v_new ``[B, Hkv, 1, D]``
+    (any batch / head stride).  Writes the new rows to ``tail[b, :, tail_len[b]]`` and returns ``[B, Hkv, G, D]``."""
+    import ctypes as C
+    lib = _lib.load()
+    B, Hkv, G, D = q.shape
+    assert tail_k.shape == tail_v.shape and tail_k.shape[0] == B and tail_k.shape[1] == Hkv and tail_k.shape[3] == D
+    assert q.is_contiguous() and tail_k.is_contiguous() and tail_v.is_contiguous() and k_cache.is_contiguous() and v_cache.is_contiguous()
+    assert k_new.shape == (B, Hkv, 1, D) and v_new.shape == (B, Hkv, 1, D) and k_new.stride(-1) == 1 and v_new.stride(-1) == 1
+    assert len(tail_len) == B
+    assert (k_start is None) == (k_len is None) and (k_start is not None or meta_host is not None)
+    assert k_start is None or (k_start.dtype == torch.int32 and k_len.dtype == torch.int32)
+    _same_device(q, k_cache, v_cache, tail_k, tail_v, k_new, v_new, workspace, out)
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty_like(q)
+    if workspace is None:
+        workspace = fork_attn_workspace(B, Hkv, G, D, q.device)
+    tl = (C.c_int32 * B)(*[int(x) for x in tail_len])
+    rc = lib.kvz_fork_attn_append(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(k_start), _ptr(k_len), int(k_len_offset),
+                                  meta_host, tail_k.data_ptr(), tail_v.data_ptr(), tail_k.shape[2], tl, k_new.data_ptr(),
+                                  v_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1), B, Hkv, G, D,
+                                  float(scale), _dtype_code(q.dtype), out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(q))
+    check(rc, "kvz_fork_attn_append")
+    return out
+
+
+def attn_merge_lse(o1: torch.Tensor, lse1: torch.Tensor, o2: torch.Tensor, lse2: torch.Tensor,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Merge two partial attention results over disjoint key sets by their natural-log LSEs (``kvz_attn_merge_lse``): o1, o2
+    ``[..., D]`` 16-bit, lse1, lse2 fp32 of the leading shape (-inf: that side saw no key)."""
+    lib = _lib.load()
+    D = o1.shape[-1]
+    rows = o1.numel() // D
+    assert o2.shape == o1.shape and o1.is_contiguous() and o2.is_contiguous() and o1.dtype == o2.dtype
+    assert lse1.numel() == rows and lse2.numel() == rows and lse1.dtype == torch.float32 and lse2.dtype == torch.float32
+    assert lse1.is_contiguous() and lse2.is_contiguous()
+    _same_device(o1, o2, lse1, lse2, out)
+    if out is None:
+        out = torch.empty_like(o1)
+    rc = lib.kvz_attn_merge_lse(o1.data_ptr(), lse1.data_ptr(), o2.data_ptr(), lse2.data_ptr(), out.data_ptr(), rows, D,
+                                _dtype_code(o1.dtype), _stream(o1))
+    check(rc, "kvz_attn_merge_lse")
+    return out
+
+
+def flash_fwd_ragged(query: torch.Tensor, k_flat: torch.Tensor, v_flat: torch.Tensor, starts: Sequence[int], lens: Sequence[int],
+                     causal: bool, softmax_scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The ragged form of ``flash_fwd``: query ``[1, H, q, D]`` over flat K, V ``[rows, D]`` in which KV head h owns rows
+    ``starts[h] : starts[h] + lens[h]`` (host lists, at most 64 heads).  Returns ``(out [Hkv, q, G, D], lse [Hkv, q, G] fp32)``;
+    rows that see no key have lse -inf."""
+    lib = _lib.load()
+    b, H, q_len, D = query.shape
+    Hkv = len(starts)
+    G = H // Hkv
+    assert b == 1 and G * Hkv == H and len(lens) == Hkv
+    assert k_flat.is_contiguous() and v_flat.is_contiguous() and k_flat.shape[-1] == D
+    rows = k_flat.numel() // D
+    assert all(0 <= s and n >= 0 and s + n <= rows for s, n in zip(starts, lens)), "a head segment runs past the buffer"
+    if query.stride(-1) != 1 or query.stride(1) % 8 or query.stride(2) % 8:
+        query = query.contiguous()
+    meta = _meta_host(list(starts), list(lens), Hkv)
+    assert meta is not None, "flash_fwd_ragged: more than 64 KV heads"
+    _same_device(query, k_flat, v_flat)
+    out = torch.empty(Hkv, q_len, G, D, dtype=query.dtype, device=query.device)
+    lse = torch.empty(Hkv, q_len, G, dtype=torch.float32, device=query.device)
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    need = int(lib.kvz_flash_workspace_bytes(Hkv, G, q_len, D))
+    ws = torch.empty(need, dtype=torch.uint8, device=query.device) if need else None
+    rc = lib.kvz_flash_fwd(query.data_ptr(), G * query.stride(1), query.stride(1), query.stride(2), k_flat.data_ptr(),
+                           v_flat.data_ptr(), None, None, 0, meta, Hkv, G, q_len, D, float(scale), 1 if causal else 0,
+                           _dtype_code(query.dtype), out.data_ptr(), q_len * G * D, D, G * D, lse.data_ptr(), _ptr(ws), need,
+                           _stream(query))
+    check(rc, "kvz_flash_fwd")
+    return out, lse
+
+
 def flash_fwd_window(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, sink: int, start: int, end: int,
                      stats: torch.Tensor, softmax_scale: Optional[float] = None) -> Optional[torch.Tensor]:
     """The dense causal forward of a scoring pass (``flash_fwd``) that also writes the row statistics of ``KVScore._get_score`` for the

@@ -119,6 +119,9 @@ class ModelKVzip:
             eos_token_id = getattr(model.generation_config, "eos_token_id", None) if hasattr(model, "generation_config") else None
         if eos_token_id is not None:
             self.gen_kwargs["eos_token_id"] = eos_token_id
+        # branches of one forked decode wave (generate_batch), besides the kernel's own limit of 64 // G: the measured per-token cost
+        # keeps falling up to that limit (profiles/fork_decode_ab.txt), so the default does not cap below it
+        self.fork_max_branches = 16
         self.sample_generator: Optional[torch.Generator] = None   # seed source of do_sample=True (None: torch's global generator)
         self.sys_prompt_ids = torch.zeros((1, 0), dtype=torch.long, device=self.device)
         self.postfix_ids = torch.zeros((1, 0), dtype=torch.long, device=self.device)
@@ -309,6 +312,57 @@ class ModelKVzip:
         elif kv.prefill_ids is not None:
             kv.prefill_ids = torch.cat([kv.prefill_ids, input_ids, a_ids], dim=1)
         return a_ids if return_ids else self.decode(a_ids)
+
+    @_on_model_device
+    @torch.inference_mode()
+    def generate_batch(self, queries, kv, return_ids: bool = False) -> list:
+        """Responses to several queries over ONE pruned cache, decoded together (no reference counterpart: the reference answers the
+        queries of a context one after the other, eval.py).  Every query becomes a branch of ``kv.fork(...)``: its first step (the
+        query tokens) runs at batch 1, then all live branches decode in one batch whose attention reads the shared context once per
+        step.  Same knobs as ``generate`` (``gen_kwargs``; the last token of every answer is dropped as there); a branch stops at EOS
+        or ``max_new_tokens`` while the others go on.  More queries than one launch takes (``64 // G`` branches, at most 16) run in
+        waves.  ``kv`` is left exactly as it was: nothing is appended to it, so there is nothing to slice; ``update_cache=True`` is
+        not offered.  Answers agree with ``generate`` up to the summation order of the attention (an argmax may tie)."""
+        ids = [self.encode(q) if isinstance(q, str) else q.to(self.device) for q in queries]
+        G = self.config.num_attention_heads // self.config.num_key_value_heads
+        wave = max(1, min(self.fork_max_branches, 64 // G))
+        answers: list = []
+        for w0 in range(0, len(ids), wave):
+            answers += self._generate_wave(ids[w0:w0 + wave], kv)
+        return answers if return_ids else [self.decode(a) for a in answers]
+
+    def _generate_wave(self, ids: List[torch.Tensor], kv) -> List[torch.Tensor]:
+        B = len(ids)
+        max_new = self.gen_kwargs["max_new_tokens"]
+        fork = kv.fork(B, tail_capacity=max(x.shape[1] for x in ids) + max_new)
+        base_len = kv.get_seq_length()
+        eos = self.eos_token_ids
+        out_ids: List[List[torch.Tensor]] = [[] for _ in range(B)]
+        cur = torch.zeros((B, 1), dtype=torch.long, device=self.device)
+        pos = torch.zeros((B, 1), dtype=torch.long, device=self.device)
+        live = [True] * B
+
+        def take(b, nxt):   # the token branch b has just produced; retire the branch at EOS / the token budget
+            out_ids[b].append(nxt)
+            cur[b] = nxt[0]
+            if (eos and int(nxt) in eos) or len(out_ids[b]) >= max_new:
+                live[b] = False
+                fork.retire(b)
+
+        for b in range(B):  # first step of every branch: its query, at batch 1
+            fork.select_branch(b)
+            n = ids[b].shape[1]
+            p = torch.arange(base_len, base_len + n, device=self.device).unsqueeze(0)
+            logits = self.model(ids[b], past_key_values=fork, use_cache=True, position_ids=p).logits[:, -1]
+            pos[b] = base_len + n
+            take(b, self.next_token(logits, self.gen_kwargs, self.sample_generator))
+        while any(live):    # one token for every live branch per step
+            logits = self.model(cur, past_key_values=fork, use_cache=True, position_ids=pos).logits[:, -1]
+            pos += 1
+            for b in range(B):
+                if live[b]:
+                    take(b, self.next_token(logits[b:b + 1], self.gen_kwargs, self.sample_generator))
+        return [torch.cat(o, dim=1)[:, :-1] for o in out_ids]
 
     def head_score(self, kv) -> torch.Tensor:
         """Per-(layer, KV head) maximum score ``[L, Hkv]`` — what the reference saves with ``--save_head_score``
