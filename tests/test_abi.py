@@ -51,6 +51,39 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SIGNATURES) == _declared_symbols()
 
 
+def _writing_entry_points():
+    """Declarations of kvzip_hip.h with a pointer parameter that is not const: the entry points that write device memory."""
+    text = open(os.path.join(ROOT, "include", "kvzip_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    out = []
+    for name, args in re.findall(r"\bint\s+(kvz_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
+        params = [a.strip() for a in args.split(",")]
+        if any("*" in a and not a.startswith("const ") for a in params):
+            out.append(name)
+    return sorted(out)
+
+
+def test_guard_band_coverage_table_names_every_writing_entry_point():
+    """tests/test_gpu_guard_bands.py calls every entry point that writes device memory on guarded buffers and says so in COVERAGE;
+    an entry point or a *_bytes size function added later cannot skip that layer silently."""
+    import test_gpu_guard_bands as gb
+    writing = [n for n in _writing_entry_points() if n not in ("kvz_prof_read",)]      # (host pointers only)
+    assert "kvz_score_chunk" in writing and "kvz_fork_attn_append" in writing and "kvz_add_i32" in writing and len(writing) >= 28
+    missing = [n for n in writing if n not in gb.COVERAGE]
+    assert not missing, f"writing entry points without a guard-band test: {missing}"
+    flushes = {"kvz_score_tail_flush", "kvz_score_tail_flush_async"}                    # (write through the pending calls' pointers)
+    assert flushes <= set(gb.COVERAGE)
+    unknown = [n for n in gb.COVERAGE if n not in _declared_symbols(("kvzip_hip.h",))]
+    assert not unknown, f"COVERAGE names entry points the header does not declare: {unknown}"
+    sizes = [s for s in _declared_symbols(("kvzip_hip.h",)) if s.endswith("_bytes")]
+    assert "kvz_score_workspace_bytes" in sizes and "kvz_fork_attn_workspace_bytes" in sizes and len(sizes) >= 6
+    used = {fn for _, fn in gb.COVERAGE.values() if fn}
+    assert not [s for s in sizes if s not in used], f"size functions no guarded buffer is sized by: {[s for s in sizes if s not in used]}"
+    src = open(os.path.join(ROOT, "tests", "test_gpu_guard_bands.py")).read().split("COVERAGE = {", 1)[1].split("\n}\n", 1)[1]
+    for name in list(gb.COVERAGE) + sizes:
+        assert re.search(r"\b%s\b" % name, src), f"{name} is listed in COVERAGE but never called in the file"
+
+
 def test_host_only_entry_points():
     from kvzip_amd import _lib
     lib = _lib.load()
