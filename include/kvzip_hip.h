@@ -163,8 +163,9 @@ int kvz_score_tail_flush_async(int handle, int slot, const void* ws, kvz_stream_
  *
  *   flat   = scores viewed as n values (any leading shape)
  *   idx    = max((int64)((double)n * ratio) - 1, 0)
- *   thres  = idx-th largest value (0-based, duplicates counted)
- *   valid  = scores > thres            (strict: ties at thres are evicted)
+ *   thres  = idx-th largest value (0-based, duplicates counted; every NaN, of either sign, ranks above +inf as in
+ *            torch.sort(descending=True): a rank inside the NaNs gives a NaN threshold)
+ *   valid  = scores > thres            (strict: ties at thres are evicted; a NaN is never kept, a NaN thres keeps nothing)
  *   ratio >= 1  ->  valid all ones, thres = 0
  *
  * scores       : n half values
@@ -195,7 +196,8 @@ int kvz_select_threshold_prehist(const void* scores, int64_t n, double ratio, in
  *   for every row of row_len scores keep exactly k = (int64)((double)row_len*ratio)
  *   entries: all values greater than the k-th largest, plus the lowest-index
  *   entries equal to it until k are kept (torch.topk's tie order is unspecified;
- *   on tie-free rows the result is identical).
+ *   on tie-free rows the result is identical).  Values compare as numbers: +0 equals
+ *   -0, and as in torch.topk every NaN ranks above +inf and equals every other NaN.
  * ------------------------------------------------------------------------- */
 int kvz_select_topk_rows(const void* scores, int64_t rows, int64_t row_len, int64_t k,
                          int dtype, uint8_t* valid_out, int32_t* row_counts,

@@ -123,12 +123,24 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 // ---- half / bf16 bit helpers ------------------------------------------------------------
 // Monotone map from the 16-bit pattern of an fp16 / bf16 value to an unsigned key such that
 // a > b (as floats)  <=>  key(a) > key(b).  (-0 maps just below +0; both compare equal to 0 as floats,
-// see select kernels for why that is harmless.)
-__host__ __device__ static inline uint32_t order_key16(uint32_t bits) {
-    return (bits & 0x8000u) ? (~bits & 0xFFFFu) : (bits | 0x8000u);
+// see select kernels for why that is harmless.)  Every NaN keys ABOVE +inf whatever its sign, as torch.sort(descending) and
+// torch.topk order it (reference attention/score.py:94,112): a NaN keeps its payload and loses its sign, so the inverse key of a NaN
+// reads back as a NaN.  `inf` = inf_bits16(dtype): a pattern is a NaN when its magnitude bits exceed it.
+__host__ __device__ constexpr static inline uint32_t inf_bits16(int dtype) { return dtype == KVZ_BF16 ? 0x7F80u : 0x7C00u; }
+__host__ __device__ static inline uint32_t order_key16(uint32_t bits, uint32_t inf) {
+    const bool neg = (bits - 0x8000u) <= inf;   // -0 .. -inf in ONE unsigned compare (bits < 2^16: a non-negative pattern wraps around)
+    return neg ? (0xFFFFu - bits) : (bits | 0x8000u);
 }
 __host__ __device__ static inline uint32_t order_key16_inv(uint32_t key) {
     return (key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu);
+}
+// The key of the VALUE: all NaNs share the top key and -0 shares the key of +0, so that key equality is equality as numbers (NaNs
+// among themselves as torch orders them: equal).  The per-row top-k breaks its ties on it.
+__host__ __device__ static inline uint32_t class_key16(uint32_t bits, uint32_t inf) {
+    const uint32_t mag = bits & 0x7FFFu;
+    if (mag > inf) return 0xFFFFu;
+    if (mag == 0u) return 0x8000u;
+    return (bits & 0x8000u) ? (~bits & 0xFFFFu) : (bits | 0x8000u);
 }
 
 __device__ static inline float half_bits_to_float(uint32_t bits, int dtype) {

@@ -2597,6 +2597,7 @@ __global__ __launch_bounds__(1024) void score_finalize_log_hist_kernel(const uin
     for (int i = threadIdx.x; i < SEL_HI_BINS; i += 1024) lh[i] = 0;
     __syncthreads();
     auto conv = [](uint32_t b) -> uint32_t { return bits16<T>((T)(b == 0u ? __builtin_nanf("") : expf(__builtin_bit_cast(float, b)))); };
+    constexpr uint32_t inf = inf_bits16(std::is_same<T, _Float16>::value ? KVZ_F16 : KVZ_BF16);  // the key ranks every NaN above +inf (kvz_common.h)
     const int64_t nvec = n >> 3;
     const int64_t stride = (int64_t)gridDim.x * 1024;
     constexpr int U = 2;   // 8-element groups in flight per thread (4 x 16-byte loads: one dependent load per iteration runs at 1.4 TB/s)
@@ -2612,7 +2613,7 @@ __global__ __launch_bounds__(1024) void score_finalize_log_hist_kernel(const uin
         for (int j = 0; j < 8; ++j) {
             const uint32_t old = (o[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
             v[j] = lw[j] == SC_LOG_EMPTY ? old : conv(lw[j]);
-            atomicAdd(&lh[order_key16(v[j]) >> 5], 1u);
+            atomicAdd(&lh[order_key16(v[j], inf) >> 5], 1u);
         }
         const u32x4 w = {v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
         reinterpret_cast<u32x4*>(out)[i] = w;
@@ -2635,7 +2636,7 @@ __global__ __launch_bounds__(1024) void score_finalize_log_hist_kernel(const uin
                 v = conv(b);
                 reinterpret_cast<uint16_t*>(out)[i] = (uint16_t)v;
             }
-            atomicAdd(&lh[order_key16(v) >> 5], 1u);
+            atomicAdd(&lh[order_key16(v, inf) >> 5], 1u);
         }
     }
     __syncthreads();

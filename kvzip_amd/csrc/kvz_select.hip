@@ -38,7 +38,7 @@ __device__ static inline void unpack8(const u32x4& v, uint32_t (&bits)[8]) {
 
 // ---- pass 1: histogram of the top 11 key bits ---------------------------------------------
 __global__ __launch_bounds__(HIST_THREADS) void select_hist_hi_kernel(const uint16_t* __restrict__ scores,
-                                                                    int64_t n, uint32_t* __restrict__ hist_hi) {
+                                                                    int64_t n, uint32_t inf, uint32_t* __restrict__ hist_hi) {
     __shared__ uint32_t lh[HI_BINS];
     for (int i = threadIdx.x; i < HI_BINS; i += HIST_THREADS) lh[i] = 0;
     __syncthreads();
@@ -48,12 +48,12 @@ __global__ __launch_bounds__(HIST_THREADS) void select_hist_hi_kernel(const uint
         uint32_t b[8];
         unpack8(v, b);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) atomicAdd(&lh[order_key16(b[j]) >> 5], 1u);
+        for (int j = 0; j < 8; ++j) atomicAdd(&lh[order_key16(b[j], inf) >> 5], 1u);
     });
     // tail (< 8 elements) handled by block 0
     if (blockIdx.x == 0) {
         for (int64_t i = (nvec << 3) + threadIdx.x; i < n; i += HIST_THREADS)
-            atomicAdd(&lh[order_key16(scores[i]) >> 5], 1u);
+            atomicAdd(&lh[order_key16(scores[i], inf) >> 5], 1u);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < HI_BINS; i += HIST_THREADS) {
@@ -108,7 +108,7 @@ __device__ static inline void find_bin_wave(const uint32_t* __restrict__ hist, u
 }
 
 // ---- pass 2: histogram of the low 5 bits inside the top bin that holds rank idx (every block finds that bin itself) -----------
-__global__ __launch_bounds__(HIST_THREADS) void select_hist_lo_kernel(const uint16_t* __restrict__ scores, int64_t n, uint64_t idx,
+__global__ __launch_bounds__(HIST_THREADS) void select_hist_lo_kernel(const uint16_t* __restrict__ scores, int64_t n, uint32_t inf, uint64_t idx,
                                                                     const uint32_t* __restrict__ hist_hi,
                                                                     uint32_t* __restrict__ hist_lo, int32_t* __restrict__ row_counts,
                                                                     int64_t rows, unsigned long long* __restrict__ kept_dev) {
@@ -129,13 +129,13 @@ __global__ __launch_bounds__(HIST_THREADS) void select_hist_lo_kernel(const uint
         unpack8(v, b);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            uint32_t key = order_key16(b[j]);
+            uint32_t key = order_key16(b[j], inf);
             if ((key >> 5) == bin) atomicAdd(&ll[key & 31u], 1u);
         }
     });
     if (blockIdx.x == 0) {
         for (int64_t i = (nvec << 3) + threadIdx.x; i < n; i += HIST_THREADS) {
-            uint32_t key = order_key16(scores[i]);
+            uint32_t key = order_key16(scores[i], inf);
             if ((key >> 5) == bin) atomicAdd(&ll[key & 31u], 1u);
         }
     }
@@ -266,7 +266,7 @@ __device__ static inline void find_bin_desc_1024(const uint32_t* hist, uint32_t 
 }
 
 __global__ __launch_bounds__(TOPK_THREADS) void select_topk_rows_kernel(const uint16_t* __restrict__ scores,
-                                                                       int64_t row_len, uint32_t k,
+                                                                       int64_t row_len, uint32_t k, uint32_t inf,
                                                                        uint8_t* __restrict__ valid_out,
                                                                        int32_t* __restrict__ row_counts) {
     __shared__ uint32_t hh[HI_BINS];
@@ -282,25 +282,26 @@ __global__ __launch_bounds__(TOPK_THREADS) void select_topk_rows_kernel(const ui
     if (t < LO_BINS) hl[t] = 0;
     if (t == 0) s_running = 0;
     __syncthreads();
-    for (int64_t i = t; i < row_len; i += TOPK_THREADS) atomicAdd(&hh[order_key16(srow[i]) >> 5], 1u);
+    for (int64_t i = t; i < row_len; i += TOPK_THREADS) atomicAdd(&hh[class_key16(srow[i], inf) >> 5], 1u);
     __syncthreads();
     uint32_t bin, rank, above;
     find_bin_desc_1024<HI_BINS>(hh, k - 1, &bin, &rank, &above);
     for (int64_t i = t; i < row_len; i += TOPK_THREADS) {
-        uint32_t key = order_key16(srow[i]);
+        uint32_t key = class_key16(srow[i], inf);
         if ((key >> 5) == bin) atomicAdd(&hl[key & 31u], 1u);
     }
     __syncthreads();
     uint32_t lo, rank2, above2;
     find_bin_desc_1024<LO_BINS>(hl, rank, &lo, &rank2, &above2);
     const uint32_t tkey = (bin << 5) | lo;
-    // elements with key > tkey: above + above2;  ties to keep (lowest index first):
+    // elements with key > tkey: above + above2;  ties to keep (lowest index first; the key is the value's class, so +0 ties with -0
+    // and a NaN with every other NaN, as they do as numbers in torch.topk):
     const uint32_t need = k - (above + above2);
 
     // ordered emit: chunks of TOPK_THREADS elements, running count of ties seen so far
     for (int64_t base = 0; base < row_len; base += TOPK_THREADS) {
         const int64_t i = base + t;
-        uint32_t key = (i < row_len) ? order_key16(srow[i]) : 0u;
+        uint32_t key = (i < row_len) ? class_key16(srow[i], inf) : 0u;
         const bool in = (i < row_len);
         const uint32_t is_tie = (in && key == tkey) ? 1u : 0u;
         // block exclusive scan of is_tie
@@ -342,12 +343,13 @@ __global__ __launch_bounds__(TOPK_THREADS) void select_small_kernel(const uint16
     if (t < LO_BINS) hl[t] = 0;
     if (t == 0) s_kept = 0;
     __syncthreads();
-    for (int i = t; i < n; i += TOPK_THREADS) atomicAdd(&hh[order_key16(scores[i]) >> 5], 1u);
+    const uint32_t inf = inf_bits16(dtype);
+    for (int i = t; i < n; i += TOPK_THREADS) atomicAdd(&hh[order_key16(scores[i], inf) >> 5], 1u);
     __syncthreads();
     uint32_t bin, r1, above;
     find_bin_desc_1024<HI_BINS>(hh, rank, &bin, &r1, &above);
     for (int i = t; i < n; i += TOPK_THREADS) {
-        const uint32_t key = order_key16(scores[i]);
+        const uint32_t key = order_key16(scores[i], inf);
         if ((key >> 5) == bin) atomicAdd(&hl[key & 31u], 1u);
     }
     __syncthreads();
@@ -468,10 +470,10 @@ static int select_threshold_impl(const void* scores, int64_t n, double ratio, in
     const uint16_t* s16 = reinterpret_cast<const uint16_t*>(scores);
     ProfScope ps("select", stream);  // the streaming passes
     if (!prehist) {
-        hipLaunchKernelGGL(select_hist_hi_kernel, dim3(blocks), dim3(HIST_THREADS), 0, stream, s16, n, hist_hi);
+        hipLaunchKernelGGL(select_hist_hi_kernel, dim3(blocks), dim3(HIST_THREADS), 0, stream, s16, n, inf_bits16(dtype), hist_hi);
         KVZ_CHECK_LAUNCH("select_hist_hi_kernel");
     }
-    hipLaunchKernelGGL(select_hist_lo_kernel, dim3(blocks), dim3(HIST_THREADS), 0, stream, s16, n, (uint64_t)idx, hist_hi, hist_lo,
+    hipLaunchKernelGGL(select_hist_lo_kernel, dim3(blocks), dim3(HIST_THREADS), 0, stream, s16, n, inf_bits16(dtype), (uint64_t)idx, hist_hi, hist_lo,
                        row_counts, rows, reinterpret_cast<unsigned long long*>(kept_dev));
     KVZ_CHECK_LAUNCH("select_hist_lo_kernel");
 
@@ -509,7 +511,7 @@ extern "C" int kvz_select_topk_rows(const void* scores, int64_t rows, int64_t ro
         return KVZ_OK;
     }
     hipLaunchKernelGGL(select_topk_rows_kernel, dim3((unsigned)rows), dim3(TOPK_THREADS), 0, stream,
-                       reinterpret_cast<const uint16_t*>(scores), row_len, (uint32_t)k, valid_out, row_counts);
+                       reinterpret_cast<const uint16_t*>(scores), row_len, (uint32_t)k, inf_bits16(dtype), valid_out, row_counts);
     KVZ_CHECK_LAUNCH("select_topk_rows_kernel");
     return KVZ_OK;
 }

@@ -528,6 +528,36 @@ def gen_full_layer(KVScore):
     np.savez_compressed(os.path.join(OUT, "g15_full_layer.npz"), **out)
 
 
+def gen_select_specials(KVScore):
+    """G16: the REFERENCE's _threshold (attention/score.py:88-102) and _threshold_uniform (:104-120) over the exhaustive and degenerate
+    selection probes (tests/select_probes.py): every 16-bit pattern - NaNs of both signs, infinities, subnormals, both zeros - and the
+    all-equal / tiny / NaN-count cases.  Stored per probe: the patterns, and per ratio the packed mask and the threshold's 16-bit
+    pattern, per k the packed top-k mask (positions among equal values are torch.topk's choice: tests compare by contract)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import select_probes as sp
+    sc = KVScore()
+    out = {}
+    for dt in sp.DTYPES:
+        for p in sp.fixture_probes(dt):
+            score = p.score
+            out[f"{p.name}/bits"] = p.bits
+            for r in p.ratios:
+                valid, thres = sc._threshold(score, r)
+                out[sp.fixture_key(p, "valid", r)] = np.packbits(valid.numpy().reshape(-1))
+                out[sp.fixture_key(p, "thres", r)] = np.array([sp.f32_to_bits(thres, dt)], dtype=np.uint16)
+            for k in p.ks:
+                N = p.bits.shape[-1]
+                if 0 < k < N:
+                    ratio = (k + 0.5) / N
+                    assert int(N * ratio) == k
+                    valid, thres = sc._threshold_uniform([score], ratio)
+                    assert thres == 0 and bool((valid.sum(-1) == k).all())
+                    out[sp.fixture_key(p, "topk", k)] = np.packbits(valid.numpy().reshape(-1))
+    path = os.path.join(OUT, "g16_select_specials.npz")
+    np.savez_compressed(path, **out)
+    print("g16", len(out), "arrays", os.path.getsize(path), "bytes", flush=True)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
@@ -550,6 +580,9 @@ def main():
     if "--only-full-layer" in sys.argv:
         gen_full_layer(KVScore)
         return
+    if "--only-select-specials" in sys.argv:
+        gen_select_specials(KVScore)
+        return
     if "--only-round5" in sys.argv:
         gen_e2e_ratios(KVScore)
         gen_uniform_ties(KVScore)
@@ -567,6 +600,7 @@ def main():
     gen_uniform_ties(KVScore)
     gen_far_context(KVScore)
     gen_full_layer(KVScore)
+    gen_select_specials(KVScore)
     total = sum(os.path.getsize(p) for p in glob.glob(os.path.join(OUT, "*.npz")))
     print(f"wrote {OUT}: {total / 1e6:.2f} MB")
 

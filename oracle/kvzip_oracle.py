@@ -94,8 +94,14 @@ def threshold(score: Union[torch.Tensor, List[torch.Tensor]], ratio: float) -> T
     if ratio < 1:
         flat = score.reshape(-1).float()
         n = max(int(flat.numel() * ratio) - 1, 0)
-        # n-th largest (0-based) == (numel-1-n)-th smallest; kthvalue is 1-based
-        thres = torch.kthvalue(flat, flat.numel() - n).values.item()
+        # n-th largest (0-based) == (numel-1-n)-th smallest; kthvalue is 1-based.  The reference's sort(descending=True) puts every
+        # NaN first, above +inf: a rank inside the NaNs gives a NaN threshold (nothing is > NaN); below them it counts finite values
+        nans = int(torch.isnan(flat).sum())
+        if n < nans:
+            thres = float("nan")
+        else:
+            fin = flat[~torch.isnan(flat)]
+            thres = torch.kthvalue(fin, fin.numel() - (n - nans)).values.item()
         valids = score.float() > thres
     else:
         valids = torch.ones_like(score, dtype=torch.bool)
@@ -124,7 +130,8 @@ def threshold_uniform(scores: Union[torch.Tensor, Sequence[torch.Tensor]], ratio
                       ) -> Tuple[torch.Tensor, int]:
     """Per (layer, head) row keep exactly k = int(N*ratio).  torch.topk's choice among tied values is
     unspecified; this oracle (and the HIP kernel) keep the LOWEST-index ties, which coincides with the
-    reference on tie-free rows."""
+    reference on tie-free rows.  Values tie as numbers: +0 with -0 and, as torch.topk ranks them, every NaN
+    with every NaN, above +inf."""
     valids = []
     for score in scores:
         if ratio < 1:
@@ -133,9 +140,10 @@ def threshold_uniform(scores: Union[torch.Tensor, Sequence[torch.Tensor]], ratio
             s = score.float()
             valid = torch.zeros_like(score, dtype=torch.bool)
             if k > 0:
-                kth = torch.kthvalue(s, n_seq - k + 1, dim=-1, keepdim=True).values  # k-th largest
-                greater = s > kth
-                ties = s == kth
+                kth = torch.sort(s, dim=-1, descending=True).values[..., k - 1:k]    # k-th largest, NaNs first
+                nan, kth_nan = torch.isnan(s), torch.isnan(kth)
+                greater = (s > kth) | (nan & ~kth_nan)
+                ties = (s == kth) | (nan & kth_nan)
                 need = k - greater.sum(-1, keepdim=True)
                 tie_rank = ties.long().cumsum(-1) - 1
                 valid = greater | (ties & (tie_rank < need))

@@ -37,8 +37,12 @@ static float half_to_float(uint16_t h, int is_bf16) {
     return f;
 }
 
+/* descending, every NaN first (above +inf), as torch.sort(descending=True) orders them: a comparison that calls a NaN equal to
+ * everything is not an order, and qsort's result with it is undefined */
 static int cmp_desc(const void* a, const void* b) {
     float x = *(const float*)a, y = *(const float*)b;
+    const int xn = x != x, yn = y != y;
+    if (xn || yn) return yn - xn;
     return (x < y) - (x > y);
 }
 
