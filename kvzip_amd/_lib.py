@@ -80,6 +80,13 @@ SIGNATURES = {
     "kvz_attn_merge_lse": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
 }
 
+# the entry points of include/kvzip_hip_tighten.h (tightening a pruned cache), bound by load() beside SIGNATURES
+EXT_SIGNATURES = {
+    "kvz_mask_resurrects": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp, _vp]),
+    "kvz_recompact_layers": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp,
+                                  _vp]),
+}
+
 _lib = None
 
 
@@ -103,6 +110,13 @@ def load() -> C.CDLL:
         raise KvzError(f"ABI version mismatch: library {lib.kvz_abi_version()} != binding {ABI_VERSION} - rebuild {LIB_PATH}")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+    for name, (res, args) in EXT_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:   # (a library built before the header existed: same ABI version, so say what to do)
+            raise KvzError(f"{LIB_PATH} does not export {name} (include/kvzip_hip_tighten.h) - rebuild it "
+                           "(`python -c 'import __graft_entry__ as g; g.build()'` or `make -C kvzip_amd/csrc`)")
         fn.restype = res
         fn.argtypes = args
     _lib = lib

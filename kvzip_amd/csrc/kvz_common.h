@@ -174,4 +174,30 @@ __device__ static inline int wave_inclusive_scan(int v) {
     return v;
 }
 
+// ---- eviction masks (kvz_compact.hip, kvz_recompact.hip) -------------------------------------------------
+// full-mask value of position p in [0, klen): ones(sink) ++ valid ++ ones(rest)
+// tok1 = 1: one mask byte per context token; tok1 = 0: ONE byte per (layer, head) row (head-level eviction,
+// reference model/wrapper.py:40-58: the whole context of a head is kept or dropped)
+__device__ static inline uint32_t full_mask4(const uint8_t* __restrict__ vrow, int p0, int sink, int N, int klen, int tok1) {
+    // returns 4 mask bits (bit j = position p0+j), positions >= klen are 0
+    uint32_t bits = 0;
+    const int c0 = p0 - sink;
+    if (tok1 && p0 >= sink && p0 + 3 < sink + N && ((reinterpret_cast<uintptr_t>(vrow + c0) & 3u) == 0)) {
+        uint32_t w = *reinterpret_cast<const uint32_t*>(vrow + c0);
+        bits = ((w & 0xFFu) ? 1u : 0u) | ((w & 0xFF00u) ? 2u : 0u) | ((w & 0xFF0000u) ? 4u : 0u) |
+               ((w & 0xFF000000u) ? 8u : 0u);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int p = p0 + j;
+            uint32_t b;
+            if (p >= klen) b = 0;
+            else if (p < sink || p >= sink + N) b = 1;
+            else b = vrow[tok1 ? p - sink : 0] ? 1u : 0u;
+            bits |= b << j;
+        }
+    }
+    return bits;
+}
+
 }  // namespace kvz

@@ -15,6 +15,7 @@ MI355X-first storage (sized for 288 GB of HBM3E):
 """
 from __future__ import annotations
 
+import copy
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -313,7 +314,9 @@ class EvictCache(_CacheBase):
 
     # reference: kvcache.py:123-138
     def prune(self, ratio: float, level: str = "pair"):
-        """Prune the KV cache.  -> (thres, real kept ratio)."""
+        """Prune the KV cache.  -> (thres, real kept ratio).  On a cache that is pruned already: ``tighten``."""
+        if self.pruned:
+            return self.tighten(ratio, level)
         thres, r_ = self._select(ratio, level)
         self.prepare_init()
         self.pruned = True
@@ -356,6 +359,65 @@ class EvictCache(_CacheBase):
             "offset": [0 for _ in range(L)],                     # rows appended after pruning, per layer
         }
         self._refresh_meta_host()
+
+    def tighten(self, ratio: float, level: str = "pair"):
+        """Prune an already pruned cache again, to a smaller ratio, from the rows it still holds (no reference counterpart: the
+        reference prunes once).  -> (thres, real kept ratio), as ``prune``.  The scores stay on the device after the first prune and
+        the masks of a falling ratio are nested at every level, so the new rows are gathered from the flat cache into fresh flat
+        buffers (``kvz_recompact_layers``; peak memory old + new pruned cache) and the cache ends up as after ``prune(ratio, level)``
+        on the dense K,V: same mask, lengths, segment starts and bytes.  Rows appended since the prune (``update_cache=True``) stay
+        behind every head's rows (slack layout; the packed layout is re-laid out only while nothing is appended).  Two host
+        synchronisations: the selection and the plan.  A ratio / level whose mask keeps a pair that was evicted raises ``ValueError``
+        and leaves the cache as it was.  The flat cache moves: forks and captured decode graphs taken before raise as they do after
+        a slack growth."""
+        if not (self.pruned and self.info.get("flatten")):
+            raise ops.KvzError("tighten: the cache is not pruned yet (prune() first)")
+        L, Hkv = self.n_layers, self.n_heads_kv
+        offsets = list(self.info["offset"])
+        if self.layout == "packed" and any(offsets):
+            raise ops.KvzError("tighten: the packed layout is re-laid out only while nothing is appended (slice() first, or use "
+                               "layout='slack')")
+        old_valid, old_evicted, old_plan = self.valid, self._evicted, self._plan
+        try:
+            thres, r_ = self._select(ratio, level)                       # host sync 1: threshold and kept count
+            plan = ops.compact_plan(self.valid, self.sink, old_plan.klen, slack=self.slack)
+            count = ops.mask_resurrects(self.valid, old_valid)
+            meta = torch.cat([plan.meta, count]).cpu()                   # host sync 2: the plan and the subset check in one copy
+            if int(meta[-1]):
+                raise ValueError(f"tighten: ratio {ratio} ({level}) keeps {int(meta[-1])} KV pairs that were evicted before - a pruned "
+                                 "cache can only be pruned further (same level, smaller ratio); prefill again for a larger one")
+        except BaseException:
+            self.valid, self._evicted = old_valid, old_evicted
+            raise
+        o = 0
+        len_h = meta[o:o + L * Hkv].view(L, Hkv); o += 2 * L * Hkv + L * (Hkv + 1)
+        max_h = meta[o:o + L]
+        rows_used = len_h.sum(-1).tolist()
+        totals = [r + Hkv * self.slack for r in rows_used]
+        src = old_plan
+        if self.slack != old_plan.slack:  # (the slack grew since the prune: the segments moved, the plan's other arrays hold)
+            src = copy.copy(old_plan)
+            src.seg_start, src.slack = torch.stack(self.info["seg_start"]), self.slack
+        ks, vs = ops.recompact_layers(self.key_cache, self.value_cache, src, old_valid, plan, self.valid, totals, tail_rows=offsets)
+        self.key_cache, self.value_cache = list(ks), list(vs)
+        self._layout_epoch += 1
+        self._plan = plan
+        self.info = {
+            "flatten": True,
+            "layout": self.layout,
+            "cu_head": self.info["cu_head"],
+            "len_k": [plan.len_k[l] for l in range(L)],
+            "len_k_host": len_h.tolist(),
+            "max_len_k": [int(x) for x in max_h.tolist()],
+            "cu_len_k": [plan.cu_len_k[l].clone() for l in range(L)],
+            "seg_start": [plan.seg_start[l] for l in range(L)],
+            "rows_used": rows_used,
+            "offset": offsets,                                           # rows appended after pruning: carried over
+        }
+        self._refresh_meta_host()
+        if self.verbose:
+            print(f"ratio {r_:.2f} ({level}), {self._mem()} GB (evict {self._evicted:.0f} pairs)")
+        return thres, r_
 
     def _refresh_meta_host(self):
         """ctypes copies [seg_start ++ len_k] per layer: passed by value to the attention kernel (slack layout only: in the packed

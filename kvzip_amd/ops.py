@@ -305,6 +305,75 @@ def compact_layers(ks: Sequence[torch.Tensor], vs: Sequence[torch.Tensor], plan:
 
 
 # --------------------------------------------------------------------------------------------------
+# tightening a pruned cache (include/kvzip_hip_tighten.h; no reference counterpart)
+# --------------------------------------------------------------------------------------------------
+def _mask_bytes(valid: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """(contiguous mask, tok1): a head-level mask (stride 0 over the context) goes down as its L*Hkv bytes, as in ``compact_plan``."""
+    if is_head_level(valid):
+        return valid[..., :1].contiguous(), 0
+    return valid.contiguous(), 1
+
+
+def mask_resurrects(new_valid: torch.Tensor, old_valid: torch.Tensor) -> torch.Tensor:
+    """Number of positions ``new_valid`` keeps although ``old_valid`` evicted them, as a device int32 ``[1]`` (no host
+    synchronisation).  Masks ``[L, 1, Hkv, N]`` / ``[L, Hkv, N]`` bool, token- or head-level each."""
+    lib = _lib.load()
+    assert new_valid.shape[-1] == old_valid.shape[-1] and new_valid.numel() == old_valid.numel()
+    _same_device(new_valid, old_valid)
+    N = new_valid.shape[-1]
+    rows = new_valid.numel() // N
+    nv, ntok1 = _mask_bytes(new_valid)
+    ov, otok1 = _mask_bytes(old_valid)
+    count = torch.empty(1, dtype=torch.int32, device=nv.device)
+    rc = lib.kvz_mask_resurrects(nv.data_ptr(), ntok1, ov.data_ptr(), otok1, rows, N, count.data_ptr(), _stream(nv))
+    check(rc, "kvz_mask_resurrects")
+    return count
+
+
+def recompact_layers(ks: Sequence[torch.Tensor], vs: Sequence[torch.Tensor], old_plan: CompactPlan, old_valid: torch.Tensor,
+                     new_plan: CompactPlan, new_valid: torch.Tensor, totals: Sequence[int],
+                     tail_rows: Optional[Sequence[int]] = None) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+    """Flat ``[rows, D]`` K, V of all layers in the layout of ``old_plan`` -> fresh buffers in the layout of ``new_plan``, ONE launch.
+    ``new_valid`` must be a subset of ``old_valid`` (``mask_resurrects`` == 0).  ``totals[l]`` = rows to allocate for layer l;
+    ``tail_rows[l]`` = rows appended behind every head of layer l after the old prune (they move behind the head's new rows)."""
+    lib = _lib.load()
+    L = len(ks)
+    assert L == old_plan.layers == new_plan.layers and len(vs) == L and len(totals) == L
+    for a in ("Hkv", "N", "sink", "klen", "ntiles"):
+        assert getattr(old_plan, a) == getattr(new_plan, a), f"the two plans differ in {a}"
+    D = ks[0].shape[-1]
+    dev = ks[0].device
+    for k, v in zip(ks, vs):
+        assert k.dim() == 2 and k.shape == v.shape and k.shape[-1] == D and k.is_contiguous() and v.is_contiguous()
+        assert k.dtype == ks[0].dtype and v.dtype == ks[0].dtype
+    tail = None
+    if tail_rows is not None and any(int(t) for t in tail_rows):
+        assert len(tail_rows) == L
+        if not 0 <= min(tail_rows) <= max(tail_rows) <= min(old_plan.slack, new_plan.slack):
+            raise KvzError(f"recompact_layers: {max(tail_rows)} appended rows per head do not fit the slack "
+                           f"({old_plan.slack} -> {new_plan.slack} rows)")
+        tail = torch.tensor([int(t) for t in tail_rows], dtype=torch.int32).to(dev)
+    ov, otok1 = _mask_bytes(old_valid)
+    nv, ntok1 = _mask_bytes(new_valid)
+    _same_device(ks[0], ov, nv, old_plan.tile_base, new_plan.tile_base)
+    k_outs = [torch.empty((max(int(t), 1), D), dtype=ks[0].dtype, device=dev)[:int(t)] for t in totals]
+    v_outs = [torch.empty((max(int(t), 1), D), dtype=ks[0].dtype, device=dev)[:int(t)] for t in totals]
+    table = torch.tensor([[t.data_ptr() for t in ks], [t.data_ptr() for t in vs],
+                          [t.data_ptr() for t in k_outs], [t.data_ptr() for t in v_outs]],
+                         dtype=torch.int64).to(dev, non_blocking=False)
+    old_seg, old_len = old_plan.seg_start.contiguous(), old_plan.len_k.contiguous()
+    rc = lib.kvz_recompact_layers(table[0].data_ptr(), table[1].data_ptr(), ov.data_ptr(), otok1, old_plan.tile_base.data_ptr(),
+                                  old_seg.data_ptr(), old_len.data_ptr(), nv.data_ptr(), ntok1, new_plan.tile_base.data_ptr(),
+                                  new_plan.seg_start.data_ptr(), new_plan.len_k.data_ptr(), _ptr(tail), L, old_plan.Hkv, old_plan.N,
+                                  old_plan.sink, old_plan.klen, D, ks[0].element_size(), table[2].data_ptr(), table[3].data_ptr(),
+                                  _stream(ks[0]))
+    check(rc, "kvz_recompact_layers")
+    # keep the pointer table alive until the kernel has consumed it
+    table.record_stream(torch.cuda.current_stream(dev))
+    return k_outs, v_outs
+
+
+# --------------------------------------------------------------------------------------------------
 # a10 / a11  append
 # --------------------------------------------------------------------------------------------------
 def update_flatten_view(cache: torch.Tensor, state: torch.Tensor, headlens: torch.Tensor,

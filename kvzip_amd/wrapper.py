@@ -394,6 +394,20 @@ class ModelKVzip:
             out.append(([ratio, round(ratio_true, 4), round(thres, 4)], fn(kv)))
         return out
 
+    def eval_ratios_evict(self, kv, ratios, fn, level: str = "pair"):
+        """``eval_ratios`` on the cache that really evicts (no reference counterpart): ONE prefill, then for every ratio
+        ``kv.prune(ratio, level)`` - the first call prunes, every later one tightens the pruned cache (``EvictCache.tighten``) -
+        and ``fn(kv)`` on a cache that decodes at the reduced size.  A pruned cache cannot take evicted pairs back, so the
+        ratios must not increase: ``ValueError`` otherwise, before the cache is touched.  Same record layout as ``eval_ratios``."""
+        ratios = list(ratios)
+        if any(b > a for a, b in zip(ratios, ratios[1:])):
+            raise ValueError(f"eval_ratios_evict: the ratios must be non-increasing (got {ratios}): an evicting cache only shrinks")
+        out = []
+        for ratio in ratios:
+            thres, ratio_true = kv.prune(ratio, level)
+            out.append(([ratio, round(ratio_true, 4), round(thres, 4)], fn(kv)))
+        return out
+
     @_on_model_device
     @torch.inference_mode()
     def _prob(self, input_ids: torch.Tensor, kv=None, device: str = "cuda") -> torch.Tensor:
