@@ -87,6 +87,13 @@ EXT_SIGNATURES = {
                                   _vp]),
 }
 
+# the entry points of include/kvzip_hip_multi.h (one decode step over several independent pruned caches), bound by load() as well
+MULTI_SIGNATURES = {
+    "kvz_multi_attn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "kvz_multi_attn_append": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _f, _i, _vp, _vp,
+                                   _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -112,13 +119,14 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in EXT_SIGNATURES.items():
-        fn = getattr(lib, name, None)
-        if fn is None:   # (a library built before the header existed: same ABI version, so say what to do)
-            raise KvzError(f"{LIB_PATH} does not export {name} (include/kvzip_hip_tighten.h) - rebuild it "
-                           "(`python -c 'import __graft_entry__ as g; g.build()'` or `make -C kvzip_amd/csrc`)")
-        fn.restype = res
-        fn.argtypes = args
+    for header, table in (("kvzip_hip_tighten.h", EXT_SIGNATURES), ("kvzip_hip_multi.h", MULTI_SIGNATURES)):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name, None)
+            if fn is None:   # (a library built before the header existed: same ABI version, so say what to do)
+                raise KvzError(f"{LIB_PATH} does not export {name} (include/{header}) - rebuild it "
+                               "(`python -c 'import __graft_entry__ as g; g.build()'` or `make -C kvzip_amd/csrc`)")
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

@@ -752,6 +752,114 @@ class ForkedCache:
         return out
 
 
+class CacheBatch:
+    """Several INDEPENDENT pruned slack-layout ``EvictCache`` objects decoding together, one token each per step (no reference
+    counterpart: batch is 1 there).  Several users, each with an own compressed context: one decode step of all live members is one
+    attention launch per layer (``kvz_multi_attn_append``), whose work items are cut from the sum of ALL members' head lengths.
+
+    The batch owns no rows and no state of its members: every member keeps its own rows in its own slack, and after a step every
+    live member is exactly as after its own ``EvictCache.update_attend`` - the new row in its slack, ``info["offset"][layer]``
+    advanced by one, ``_seen_tokens`` advanced at layer 0.  A member can therefore be used alone, sliced, tightened or continued with
+    ``update_cache=True`` between or after the steps.  A member whose layout changed since the last step (slack growth, ``tighten``)
+    makes the batch rebuild its segment table (host arrays of addresses, starts and lengths; no tensor of a member is held between
+    calls).  Offsets may differ between members and between calls.
+
+    Hook for the attention adapter (``kvzip_amd.attn``): ``update_attend`` - ``[B, H, 1, D]`` queries, one new token per live member.
+    First steps (``q_len > 1``) do not go through the batch: they run at batch 1 on each member's own path."""
+
+    def __init__(self, caches):
+        caches = list(caches)
+        if not caches:
+            raise ops.KvzError("cache batch: needs at least one cache")
+        for c in caches:
+            if not isinstance(c, EvictCache):
+                raise ops.KvzError(f"cache batch: members are pruned EvictCache objects in the slack layout (got {type(c).__name__}: "
+                                   "forks share one cache - kvz_fork_attn_append is their launch - and a RetainCache never evicts)")
+            if not (c.pruned and c.info.get("flatten")):
+                raise ops.KvzError("cache batch: a member is not pruned yet (prune() first)")
+            if c.layout != "slack":
+                raise ops.KvzError("cache batch: a member is in the packed layout (its segments move with every appended token); "
+                                   "layout='slack' is what the batched decode step appends to")
+        if len({id(c) for c in caches}) != len(caches):
+            raise ops.KvzError("cache batch: the same cache twice (two rows of one step would land in one slot)")
+        c0 = caches[0]
+        for c in caches[1:]:
+            if (c.n_heads_kv, c.n_group_kv, c.n_layers, c.dtype) != (c0.n_heads_kv, c0.n_group_kv, c0.n_layers, c0.dtype):
+                raise ops.KvzError("cache batch: the members differ in geometry (KV heads, query heads per KV head, layers, dtype): "
+                                   f"({c.n_heads_kv}, {c.n_group_kv}, {c.n_layers}, {c.dtype}) vs "
+                                   f"({c0.n_heads_kv}, {c0.n_group_kv}, {c0.n_layers}, {c0.dtype})")
+            if c.device != c0.device:
+                raise ops.KvzError(f"cache batch: the members live on {c0.device} and {c.device}: one launch works on ONE device")
+        B = len(caches)
+        if (B > ops.MULTI_MAX_CACHES or B * c0.n_heads_kv > ops.MULTI_MAX_SEGMENTS or c0.n_heads_kv > ops.MULTI_MAX_HEADS
+                or c0.n_group_kv > ops.MULTI_MAX_GROUP):
+            raise ops.KvzError(f"cache batch: {B} caches x {c0.n_heads_kv} KV heads x {c0.n_group_kv} query heads per KV head: one "
+                               f"launch takes at most {ops.MULTI_MAX_CACHES} caches, {ops.MULTI_MAX_SEGMENTS} segments (caches x KV "
+                               f"heads), {ops.MULTI_MAX_HEADS} KV heads and {ops.MULTI_MAX_GROUP} query heads per KV head")
+        self.caches, self.n_caches = caches, B
+        self.n_layers, self.n_heads_kv, self.n_group_kv = c0.n_layers, c0.n_heads_kv, c0.n_group_kv
+        self.device, self.dtype = c0.device, c0.dtype
+        self.pruned, self.get_score, self.layout = True, False, "multi"
+        self.active = [True] * B
+        self._tables: Optional[List[ops.MultiTable]] = None   # per layer; valid while the members' layout epochs are _epochs
+        self._epochs: Optional[Tuple[int, ...]] = None
+        self._ws = None
+
+    def get_seq_length(self, layer_idx: Optional[int] = 0) -> int:
+        return max(c.get_seq_length(layer_idx) for c in self.caches)
+
+    def retire(self, b: int) -> None:
+        """Member ``b`` is finished (EOS, token budget): later steps skip it (no write, no work item, zero output rows)."""
+        self.active[b] = False
+
+    def _table(self, layer_idx: int) -> "ops.MultiTable":
+        epochs = tuple(c._layout_epoch for c in self.caches)
+        if self._tables is None or epochs != self._epochs:
+            Hkv = self.n_heads_kv
+            metas = [c.info["meta_host"] for c in self.caches]
+            self._tables = [ops.MultiTable([c.key_cache[l] for c in self.caches], [c.value_cache[l] for c in self.caches],
+                                           [list(m[l][:Hkv]) for m in metas], [list(m[l][Hkv:2 * Hkv]) for m in metas],
+                                           [c.slack for c in self.caches]) for l in range(self.n_layers)]
+            self._epochs = epochs
+        return self._tables[layer_idx]
+
+    def update_attend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
+                      softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Decode step of all members: query ``[B, H, 1, D]``, key / value ``[B, Hkv, 1, D]`` -> ``[B, Hkv, G, D]``.  Live members get
+        their new row appended to their own slack and their bookkeeping advanced as by ``EvictCache.update_attend``; retired ones are
+        skipped (their output rows are zero)."""
+        B, _, q_len, D = query_states.shape
+        if B != self.n_caches or q_len != 1:
+            raise ops.KvzError(f"cache batch: a decode step takes [{self.n_caches}, H, 1, D] queries (got batch {B}, {q_len} positions): "
+                               "first steps run at batch 1 on each cache's own path")
+        offsets = []
+        for c, live in zip(self.caches, self.active):
+            if not live:
+                offsets.append(-1)
+                continue
+            if not (c.pruned and c.info.get("flatten") and c.layout == "slack"):
+                raise ops.KvzError("cache batch: a member is no longer a pruned slack-layout cache")
+            off = c.info["offset"][layer_idx]
+            if off + 1 > c.slack:
+                c._grow_slack(off + 1)      # (bumps the member's layout epoch: the table below is rebuilt)
+            offsets.append(off)
+        table = self._table(layer_idx)
+        if key_states.stride(-1) != 1 or value_states.stride(-1) != 1 or key_states.stride(0) % 8 or key_states.stride(1) % 8 \
+                or value_states.stride(0) % 8 or value_states.stride(1) % 8:
+            key_states, value_states = key_states.contiguous(), value_states.contiguous()
+        if self._ws is None or self._ws[0] != D:
+            self._ws = (D, ops.multi_attn_workspace(B, self.n_heads_kv, self.n_group_kv, D, self.device))
+        q = query_states.reshape(B, self.n_heads_kv, self.n_group_kv, D).contiguous()
+        out = ops.multi_attn_append(q, table, offsets, key_states, value_states, softmax_scale=softmax_scale, workspace=self._ws[1],
+                                    out=out)
+        for c, off in zip(self.caches, offsets):
+            if off >= 0:
+                c.info["offset"][layer_idx] = off + 1
+                if layer_idx == 0:
+                    c._seen_tokens += 1
+        return out
+
+
 class RetainCache(_CacheBase):
     """KV cache that keeps the full KV in memory and subsamples it at every attention call, so that several
     compression ratios can be evaluated from a single prefill (reference attention/kvcache.py:216-347).

@@ -581,6 +581,75 @@ def attn_merge_lse(o1: torch.Tensor, lse1: torch.Tensor, o2: torch.Tensor, lse2:
     return out
 
 
+# --------------------------------------------------------------------------------------------------
+# batched decode: one token for several INDEPENDENT pruned caches (include/kvzip_hip_multi.h; no reference counterpart)
+# --------------------------------------------------------------------------------------------------
+MULTI_MAX_CACHES = 16       # caches of one batched decode launch
+MULTI_MAX_SEGMENTS = 128    # caches x KV heads
+MULTI_MAX_HEADS = 64
+MULTI_MAX_GROUP = 64        # query heads per KV head
+
+
+class MultiTable:
+    """The segments of B slack-layout caches (one layer) as the host arrays ``kvz_multi_attn_append`` takes: made once per layout of
+    the caches, so that a decode step builds nothing but its B offsets.  Holds ADDRESSES, not tensors: whoever keeps a table keeps
+    the caches and makes a new one when a cache was re-laid out (``kvcache.CacheBatch``)."""
+
+    def __init__(self, k_caches: Sequence[torch.Tensor], v_caches: Sequence[torch.Tensor], seg_starts: Sequence[Sequence[int]],
+                 lens: Sequence[Sequence[int]], slacks: Sequence[int]):
+        import ctypes as C
+        B = len(k_caches)
+        assert B >= 1 and len(v_caches) == B and len(seg_starts) == B and len(lens) == B and len(slacks) == B
+        Hkv = len(seg_starts[0])
+        assert all(len(s) == Hkv for s in seg_starts) and all(len(n) == Hkv for n in lens)
+        _same_device(*k_caches, *v_caches)
+        for k, v in zip(k_caches, v_caches):
+            assert k.is_contiguous() and v.is_contiguous() and k.shape == v.shape and k.dtype == k_caches[0].dtype
+            assert k.shape[-1] == k_caches[0].shape[-1]
+        self.B, self.Hkv, self.D, self.dtype, self.device = B, Hkv, k_caches[0].shape[-1], k_caches[0].dtype, k_caches[0].device
+        self.k_ptrs = (C.c_void_p * B)(*[k.data_ptr() for k in k_caches])
+        self.v_ptrs = (C.c_void_p * B)(*[v.data_ptr() for v in v_caches])
+        self.seg = (C.c_int32 * (B * Hkv))(*[int(x) for s in seg_starts for x in s])
+        self.lens = (C.c_int32 * (B * Hkv))(*[int(x) for n in lens for x in n])
+        self.slack = (C.c_int32 * B)(*[int(x) for x in slacks])
+
+
+def multi_attn_workspace(B: int, Hkv: int, G: int, D: int, device) -> torch.Tensor:
+    """Scratch of ``multi_attn_append`` (partials of the key ranges); no initialisation needed, no dependence on the key lengths."""
+    need = _lib.load().kvz_multi_attn_workspace_bytes(B, Hkv, G, D)
+    return torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+
+
+def multi_attn_append(q: torch.Tensor, table: MultiTable, offsets: Sequence[int], k_new: torch.Tensor, v_new: torch.Tensor,
+                      softmax_scale: Optional[float] = None, workspace: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One decode step of B independent caches in one launch (``kvz_multi_attn_append``).  q ``[B, Hkv, G, D]``; ``table`` the
+    caches' segments; ``offsets[b]`` rows appended to cache b before this call (-1: inactive cache - nothing of it is read or
+    written, its output rows are zero); k_new / v_new ``[B, Hkv, 1, D]`` (any batch / head stride).  Writes the new rows to row
+    ``seg_start + len + offset`` of every head segment of every live cache and returns ``[B, Hkv, G, D]``."""
+    import ctypes as C
+    lib = _lib.load()
+    B, Hkv, G, D = q.shape
+    assert table.B == B and table.Hkv == Hkv and table.D == D and table.dtype == q.dtype and len(offsets) == B
+    assert q.is_contiguous()
+    assert k_new.shape == (B, Hkv, 1, D) and v_new.shape == (B, Hkv, 1, D) and k_new.stride(-1) == 1 and v_new.stride(-1) == 1
+    _same_device(q, k_new, v_new, workspace, out)
+    if q.device != table.device:
+        raise KvzError(f"all tensors of a call must live on one device (got {q.device} and the caches on {table.device})")
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty_like(q)
+    assert out.is_contiguous() and out.shape == q.shape
+    if workspace is None:
+        workspace = multi_attn_workspace(B, Hkv, G, D, q.device)
+    off = (C.c_int32 * B)(*[int(x) for x in offsets])
+    rc = lib.kvz_multi_attn_append(q.data_ptr(), table.k_ptrs, table.v_ptrs, table.seg, table.lens, table.slack, off, k_new.data_ptr(),
+                                   v_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1), B, Hkv, G, D,
+                                   float(scale), _dtype_code(q.dtype), out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(q))
+    check(rc, "kvz_multi_attn_append")
+    return out
+
+
 def flash_fwd_ragged(query: torch.Tensor, k_flat: torch.Tensor, v_flat: torch.Tensor, starts: Sequence[int], lens: Sequence[int],
                      causal: bool, softmax_scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The ragged form of ``flash_fwd``: query ``[1, H, q, D]`` over flat K, V ``[rows, D]`` in which KV head h owns rows

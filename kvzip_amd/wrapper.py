@@ -23,7 +23,7 @@ from typing import List, Optional, Tuple, Union
 
 import torch
 
-from .kvcache import EvictCache, RetainCache
+from .kvcache import CacheBatch, EvictCache, RetainCache
 from .monkeypatch import replace_attn
 from .ops import KvzError
 from .template import template
@@ -122,6 +122,7 @@ class ModelKVzip:
         # branches of one forked decode wave (generate_batch), besides the kernel's own limit of 64 // G: the measured per-token cost
         # keeps falling up to that limit (profiles/fork_decode_ab.txt), so the default does not cap below it
         self.fork_max_branches = 16
+        self.multi_max_caches = 16   # caches of one batched decode wave (generate_multi), besides the kernel's own limit of 128 // Hkv
         self.sample_generator: Optional[torch.Generator] = None   # seed source of do_sample=True (None: torch's global generator)
         self.sys_prompt_ids = torch.zeros((1, 0), dtype=torch.long, device=self.device)
         self.postfix_ids = torch.zeros((1, 0), dtype=torch.long, device=self.device)
@@ -363,6 +364,67 @@ class ModelKVzip:
                 if live[b]:
                     take(b, self.next_token(logits[b:b + 1], self.gen_kwargs, self.sample_generator))
         return [torch.cat(o, dim=1)[:, :-1] for o in out_ids]
+
+    @_on_model_device
+    @torch.inference_mode()
+    def generate_multi(self, queries, kvs, update_cache: bool = False, return_ids: bool = False) -> list:
+        """Responses to one query PER CACHE, decoded together (no reference counterpart: batch is 1 there): ``queries[i]`` is
+        answered over ``kvs[i]``, a pruned slack-layout ``EvictCache`` of its own - several users, each with an own compressed
+        context.  Every query's first step (its tokens) runs at batch 1 on its own cache through the path ``generate`` takes; then
+        all live sequences decode in one batch, one token each per step, whose attention is one launch per layer over all the caches
+        (``kvcache.CacheBatch``) and whose other layers read the model's weights once for the whole batch.  Same knobs as ``generate``
+        (``gen_kwargs``; the last token of every answer is dropped as there); a sequence stops at EOS or ``max_new_tokens`` while the
+        others go on.  Afterwards every cache is sliced back to its previous length unless ``update_cache=True`` (multi-turn:
+        ``prefill_ids`` grows as in ``generate``), and is an ordinary ``EvictCache`` again either way.  More caches than one launch
+        takes (16, or ``128 // Hkv``) run in waves.  Answers agree with ``generate`` up to the summation order of the attention (an
+        argmax may tie); with ``do_sample=True`` the draws of the sequences interleave."""
+        kvs = list(kvs)
+        ids = [self.encode(q) if isinstance(q, str) else q.to(self.device) for q in queries]
+        if len(ids) != len(kvs):
+            raise ValueError(f"generate_multi: {len(ids)} queries for {len(kvs)} caches (one query per cache)")
+        wave = max(1, min(self.multi_max_caches, 16, 128 // self.config.num_key_value_heads))
+        answers: list = []
+        for w0 in range(0, len(ids), wave):
+            answers += self._generate_multi_wave(ids[w0:w0 + wave], kvs[w0:w0 + wave], update_cache)
+        return answers if return_ids else [self.decode(a) for a in answers]
+
+    def _generate_multi_wave(self, ids: List[torch.Tensor], kvs: list, update_cache: bool) -> List[torch.Tensor]:
+        B = len(ids)
+        if B == 1:   # (nothing to share: the sequential path)
+            return [self.generate(ids[0], kv=kvs[0], update_cache=update_cache, return_ids=True)]
+        batch = CacheBatch(kvs)
+        max_new = self.gen_kwargs["max_new_tokens"]
+        eos = self.eos_token_ids
+        seen_prev = [kv._seen_tokens for kv in kvs]
+        out_ids: List[List[torch.Tensor]] = [[] for _ in range(B)]
+        cur = torch.zeros((B, 1), dtype=torch.long, device=self.device)
+        pos = torch.zeros((B, 1), dtype=torch.long, device=self.device)
+        live = [True] * B
+
+        def take(b, nxt):   # the token sequence b has just produced; retire it at EOS / the token budget
+            out_ids[b].append(nxt)
+            cur[b] = nxt[0]
+            if (eos and int(nxt) in eos) or len(out_ids[b]) >= max_new:
+                live[b] = False
+                batch.retire(b)
+
+        for b in range(B):  # first step of every sequence: its query on its own cache, at batch 1
+            logits = self.model(ids[b], past_key_values=kvs[b], use_cache=True).logits[:, -1]
+            pos[b] = kvs[b].get_seq_length()          # (the caches have different lengths: explicit positions from here on)
+            take(b, self.next_token(logits, self.gen_kwargs, self.sample_generator))
+        while any(live):    # one token for every live sequence per step
+            logits = self.model(cur, past_key_values=batch, use_cache=True, position_ids=pos).logits[:, -1]
+            pos += 1
+            for b in range(B):
+                if live[b]:
+                    take(b, self.next_token(logits[b:b + 1], self.gen_kwargs, self.sample_generator))
+        answers = [torch.cat(o, dim=1)[:, :-1] for o in out_ids]   # (the last token is dropped: see generate)
+        for b, kv in enumerate(kvs):
+            if not update_cache:
+                kv.slice(seen_prev[b])
+            elif kv.prefill_ids is not None:
+                kv.prefill_ids = torch.cat([kv.prefill_ids, ids[b], answers[b]], dim=1)
+        return answers
 
     def head_score(self, kv) -> torch.Tensor:
         """Per-(layer, KV head) maximum score ``[L, Hkv]`` — what the reference saves with ``--save_head_score``
