@@ -94,6 +94,13 @@ MULTI_SIGNATURES = {
                                    _sz, _vp]),
 }
 
+# the entry points of include/kvzip_hip_prefill.h (the packed first step of a forked decode), bound by load() as well
+PREFILL_SIGNATURES = {
+    "kvz_fork_prefill_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "kvz_fork_prefill_tail": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i,
+                                   _i, _i, _f, _i, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -119,7 +126,8 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
-    for header, table in (("kvzip_hip_tighten.h", EXT_SIGNATURES), ("kvzip_hip_multi.h", MULTI_SIGNATURES)):
+    for header, table in (("kvzip_hip_tighten.h", EXT_SIGNATURES), ("kvzip_hip_multi.h", MULTI_SIGNATURES),
+                          ("kvzip_hip_prefill.h", PREFILL_SIGNATURES)):
         for name, (res, args) in table.items():
             fn = getattr(lib, name, None)
             if fn is None:   # (a library built before the header existed: same ABI version, so say what to do)

@@ -16,7 +16,7 @@ MI355X-first storage (sized for 288 GB of HBM3E):
 from __future__ import annotations
 
 import copy
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -623,7 +623,9 @@ class ForkedCache:
 
     Hooks for the attention adapter (``kvzip_amd.attn``):
       * ``first_step`` - the query of ONE branch (``select_branch`` names it), ``q_len > 1``: ``kvz_flash_fwd`` over the shared
-        segments (no mask) and over the branch's tail (causal), merged by their LSEs;
+        segments (no mask) and over the branch's tail (causal), merged by their LSEs; or, after ``select_packed``, the queries of
+        SEVERAL branches back to back in one pass: one ``kvz_flash_fwd`` over the shared segments for all positions and one
+        ``kvz_fork_prefill_tail`` for everything branch-private (append, causal attention inside each branch's tail, merge);
       * ``update_attend`` - ``[B, H, 1, D]`` queries, one new token per live branch.
     The fork never changes ``info["offset"]``, ``_seen_tokens`` or any row of the base cache.  A prune or a slack growth of the base
     moves the rows the fork points at: every hook then raises ``KvzError`` (as ``DecodeGraph.replay`` does)."""
@@ -658,6 +660,7 @@ class ForkedCache:
         self.tail_len = [[0] * self.n_branches for _ in range(self.n_layers)]
         self.active = [True] * self.n_branches
         self._branch = 0
+        self._packed: Optional[Tuple[List[int], List[int]]] = None   # (branches, lengths) of the next forward pass (select_packed)
         self._ws = None
 
     # -- bookkeeping ---------------------------------------------------------------------------------
@@ -668,6 +671,25 @@ class ForkedCache:
         """The branch the next ``first_step`` calls belong to."""
         assert 0 <= b < self.n_branches
         self._branch = int(b)
+
+    def select_packed(self, branches: Sequence[int], lengths: Sequence[int]) -> None:
+        """The next forward pass carries the queries of ``branches`` (distinct, live) back to back, ``lengths[i]`` tokens of
+        ``branches[i]`` each: every layer's ``first_step`` then takes ``sum(lengths)`` positions.  Cleared after the last layer's call."""
+        branches, lengths = [int(b) for b in branches], [int(n) for n in lengths]
+        if len(branches) != len(lengths):
+            raise ops.KvzError(f"forked cache: select_packed got {len(branches)} branches and {len(lengths)} lengths")
+        if not branches:
+            raise ops.KvzError("forked cache: select_packed needs at least one branch")
+        if len(set(branches)) != len(branches):
+            raise ops.KvzError(f"forked cache: select_packed names a branch twice ({branches}): its rows would land in one tail twice")
+        for b, n in zip(branches, lengths):
+            if not 0 <= b < self.n_branches:
+                raise ops.KvzError(f"forked cache: select_packed: no branch {b} (the fork has {self.n_branches})")
+            if not self.active[b]:
+                raise ops.KvzError(f"forked cache: select_packed: branch {b} is retired")
+            if n < 0:
+                raise ops.KvzError(f"forked cache: select_packed: branch {b} has a negative length {n}")
+        self._packed = (branches, lengths)
 
     def retire(self, b: int) -> None:
         """Branch ``b`` is finished (EOS, token budget): later decode steps skip it (no write, zero output rows)."""
@@ -702,8 +724,11 @@ class ForkedCache:
                    softmax_scale: Optional[float] = None) -> torch.Tensor:
         """The query of the selected branch: query ``[1, H, q, D]``, key / value ``[1, Hkv, q, D]``.  Appends the K,V rows to the
         branch's tail and returns the attention over shared segment ++ tail (bottom-right causal inside the tail) as
-        ``[Hkv, q, G, D]``."""
+        ``[Hkv, q, G, D]``.  With a packing selected (``select_packed``): the queries of its branches back to back, same shapes with
+        ``q = sum(lengths)``; every branch's rows go to its own tail and see only the shared segments and that tail."""
         self._check(layer_idx)
+        if self._packed is not None:
+            return self._first_step_packed(query_states, key_states, value_states, layer_idx, softmax_scale)
         b = self._branch
         bsz, _, q_len, D = query_states.shape
         if bsz != 1:
@@ -725,6 +750,30 @@ class ForkedCache:
                                       [t + q_len] * Hkv, causal=True, softmax_scale=softmax_scale)
         self.tail_len[layer_idx][b] = t + q_len
         return ops.attn_merge_lse(o1, l1, o2, l2, out=o1)
+
+    def _first_step_packed(self, query_states, key_states, value_states, layer_idx, softmax_scale):
+        branches, lengths = self._packed
+        bsz, _, T, D = query_states.shape
+        if bsz != 1 or T != sum(lengths):
+            raise ops.KvzError(f"forked cache: the packed first step takes [1, H, {sum(lengths)}, D] queries, the lengths "
+                               f"{lengths} of branches {branches} back to back (got batch {bsz}, {T} positions)")
+        tlen = self.tail_len[layer_idx]
+        tk, tv = self._tails(layer_idx, max(tlen[b] + n for b, n in zip(branches, lengths)), D)
+        o, lse = ops.flash_fwd_ragged(query_states, self._k[layer_idx], self._v[layer_idx], self._starts[layer_idx],
+                                      self._lens[layer_idx], causal=False, softmax_scale=softmax_scale)
+        # the runs of positions in packing order, then the branches that take no part (empty runs at the end)
+        order = branches + [b for b in range(self.n_branches) if b not in branches]
+        cu = [0]
+        for n in lengths:
+            cu.append(cu[-1] + n)
+        cu += [T] * (self.n_branches - len(branches))
+        ops.fork_prefill_tail(query_states, cu, tk, tv, tlen, key_states, value_states, o, lse, softmax_scale=softmax_scale, out=o,
+                              branches=order)
+        for b, n in zip(branches, lengths):
+            tlen[b] += n
+        if layer_idx == self.n_layers - 1:
+            self._packed = None
+        return o
 
     def update_attend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
                       softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -581,6 +581,58 @@ def attn_merge_lse(o1: torch.Tensor, lse1: torch.Tensor, o2: torch.Tensor, lse2:
     return out
 
 
+def fork_prefill_tail(query: torch.Tensor, cu_q: Sequence[int], tail_k: torch.Tensor, tail_v: torch.Tensor, tail_len: Sequence[int],
+                      k_new: torch.Tensor, v_new: torch.Tensor, o_shared: torch.Tensor, lse_shared: torch.Tensor,
+                      softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                      branches: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """The branch-private part of a PACKED first step (``kvz_fork_prefill_tail``, include/kvzip_hip_prefill.h): the queries of B
+    branches back to back, branch b owning positions ``cu_q[b] : cu_q[b + 1]`` (host list of B + 1, ``cu_q[0] = 0``; an empty branch
+    takes no part).  query ``[1, H, T, D]``, k_new / v_new ``[1, Hkv, T, D]`` (any head / position stride, rows contiguous); tail_k /
+    tail_v ``[B, Hkv, tail_cap, D]`` with ``tail_len[b]`` rows in use; ``(o_shared [Hkv, T, G, D], lse_shared [Hkv, T, G])`` the
+    partial result over the shared segments (``flash_fwd_ragged(..., causal=False)``).  Appends every branch's rows to its tail,
+    attends every position over its own branch's tail (bottom-right causal) and returns the merge with the shared partial,
+    ``[Hkv, T, G, D]``; ``out`` may be ``o_shared``.  ``branches``: a permutation of ``range(B)`` when the packing does not name the
+    branches in ascending order - the b-th run of positions then belongs to tail ``branches[b]`` (``tail_len`` stays indexed by tail)."""
+    import ctypes as C
+    lib = _lib.load()
+    b1, H, T, D = query.shape
+    B, Hkv = tail_k.shape[0], tail_k.shape[1]
+    G = H // Hkv
+    assert b1 == 1 and G * Hkv == H and len(cu_q) == B + 1 and len(tail_len) == B
+    assert tail_k.shape == tail_v.shape and tail_k.shape[3] == D and tail_k.is_contiguous() and tail_v.is_contiguous()
+    assert k_new.shape == (1, Hkv, T, D) and v_new.shape == (1, Hkv, T, D)
+    assert o_shared.shape == (Hkv, T, G, D) and o_shared.is_contiguous() and o_shared.dtype == query.dtype
+    assert lse_shared.shape == (Hkv, T, G) and lse_shared.is_contiguous() and lse_shared.dtype == torch.float32
+    if int(cu_q[B]) != T:
+        raise KvzError(f"fork_prefill_tail: cu_q ends at {int(cu_q[B])}, the packed query holds {T} positions")
+    if query.stride(-1) != 1 or query.stride(1) % 8 or query.stride(2) % 8:
+        query = query.contiguous()
+    if k_new.stride(-1) != 1 or k_new.stride(1) % 8 or k_new.stride(2) % 8:
+        k_new = k_new.contiguous()
+    if v_new.stride(-1) != 1 or v_new.stride(1) % 8 or v_new.stride(2) % 8:
+        v_new = v_new.contiguous()
+    _same_device(query, tail_k, tail_v, k_new, v_new, o_shared, lse_shared, out)
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty_like(o_shared)
+    assert out.shape == o_shared.shape and out.is_contiguous() and out.dtype == o_shared.dtype
+    if T == 0:   # (nothing packed: nothing to launch - and an empty tensor has no address to hand over)
+        return out
+    need = int(lib.kvz_fork_prefill_workspace_bytes(T, B, Hkv, G, D))
+    ws = torch.empty(need, dtype=torch.uint8, device=query.device) if need else None
+    cu = (C.c_int32 * (B + 1))(*[int(x) for x in cu_q])
+    tl = (C.c_int32 * B)(*[int(x) for x in tail_len])
+    assert branches is None or len(branches) == B
+    br = None if branches is None else (C.c_int32 * B)(*[int(x) for x in branches])
+    rc = lib.kvz_fork_prefill_tail(query.data_ptr(), G * query.stride(1), query.stride(1), query.stride(2), cu, tail_k.data_ptr(),
+                                   tail_v.data_ptr(), tail_k.shape[2], tl, k_new.data_ptr(), v_new.data_ptr(), k_new.stride(1),
+                                   k_new.stride(2), v_new.stride(1), v_new.stride(2), o_shared.data_ptr(), lse_shared.data_ptr(),
+                                   out.data_ptr(), br, B, Hkv, G, D, float(scale), _dtype_code(query.dtype), _ptr(ws), need,
+                                   _stream(query))
+    check(rc, "kvz_fork_prefill_tail")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # batched decode: one token for several INDEPENDENT pruned caches (include/kvzip_hip_multi.h; no reference counterpart)
 # --------------------------------------------------------------------------------------------------

@@ -122,6 +122,9 @@ class ModelKVzip:
         # branches of one forked decode wave (generate_batch), besides the kernel's own limit of 64 // G: the measured per-token cost
         # keeps falling up to that limit (profiles/fork_decode_ab.txt), so the default does not cap below it
         self.fork_max_branches = 16
+        # generate_batch: the first steps of all branches of a wave as ONE packed forward pass (kvcache.ForkedCache.select_packed:
+        # the shared context and the model's weights are read once per wave instead of once per query); False: one forward per branch
+        self.fork_packed_first = True
         self.multi_max_caches = 16   # caches of one batched decode wave (generate_multi), besides the kernel's own limit of 128 // Hkv
         self.sample_generator: Optional[torch.Generator] = None   # seed source of do_sample=True (None: torch's global generator)
         self.sys_prompt_ids = torch.zeros((1, 0), dtype=torch.long, device=self.device)
@@ -318,8 +321,9 @@ class ModelKVzip:
     @torch.inference_mode()
     def generate_batch(self, queries, kv, return_ids: bool = False) -> list:
         """Responses to several queries over ONE pruned cache, decoded together (no reference counterpart: the reference answers the
-        queries of a context one after the other, eval.py).  Every query becomes a branch of ``kv.fork(...)``: its first step (the
-        query tokens) runs at batch 1, then all live branches decode in one batch whose attention reads the shared context once per
+        queries of a context one after the other, eval.py).  Every query becomes a branch of ``kv.fork(...)``: the first steps (the
+        query tokens) of all branches of a wave run as ONE packed forward pass (``fork_packed_first``, the default; ``False``: one
+        forward per branch at batch 1), then all live branches decode in one batch whose attention reads the shared context once per
         step.  Same knobs as ``generate`` (``gen_kwargs``; the last token of every answer is dropped as there); a branch stops at EOS
         or ``max_new_tokens`` while the others go on.  More queries than one launch takes (``64 // G`` branches, at most 16) run in
         waves.  ``kv`` is left exactly as it was: nothing is appended to it, so there is nothing to slice; ``update_cache=True`` is
@@ -331,6 +335,13 @@ class ModelKVzip:
         for w0 in range(0, len(ids), wave):
             answers += self._generate_wave(ids[w0:w0 + wave], kv)
         return answers if return_ids else [self.decode(a) for a in answers]
+
+    def _packs_first_steps(self, lengths: List[int]) -> bool:
+        """Whether a wave of queries of these lengths takes the packed first step.  Every wave of two or more does: packed was faster
+        than one pass per branch at every measured shape (2-9 queries of 16-160 tokens, 1.5-6.1 x; profiles/fork_prefill_ab.txt,
+        DESIGN 3.10), so there is no shape rule - one would go HERE.  (An empty query has no last position to take a token from: it
+        goes to the per-branch loop, which fails on it as it always did.)"""
+        return bool(self.fork_packed_first) and all(n > 0 for n in lengths)
 
     def _generate_wave(self, ids: List[torch.Tensor], kv) -> List[torch.Tensor]:
         B = len(ids)
@@ -350,13 +361,25 @@ class ModelKVzip:
                 live[b] = False
                 fork.retire(b)
 
-        for b in range(B):  # first step of every branch: its query, at batch 1
-            fork.select_branch(b)
-            n = ids[b].shape[1]
-            p = torch.arange(base_len, base_len + n, device=self.device).unsqueeze(0)
-            logits = self.model(ids[b], past_key_values=fork, use_cache=True, position_ids=p).logits[:, -1]
-            pos[b] = base_len + n
-            take(b, self.next_token(logits, self.gen_kwargs, self.sample_generator))
+        lens = [x.shape[1] for x in ids]
+        if B >= 2 and self._packs_first_steps(lens):
+            # first steps of all branches in ONE forward pass: the queries back to back, every one at the positions behind the context
+            fork.select_packed(list(range(B)), lens)
+            p = torch.cat([torch.arange(base_len, base_len + n, device=self.device) for n in lens]).unsqueeze(0)
+            logits = self.model(torch.cat(ids, dim=1), past_key_values=fork, use_cache=True, position_ids=p).logits
+            end = 0
+            for b, n in enumerate(lens):   # the next token of a branch comes from its last packed position
+                end += n
+                pos[b] = base_len + n
+                take(b, self.next_token(logits[:, end - 1], self.gen_kwargs, self.sample_generator))
+        else:
+            for b in range(B):  # first step of every branch: its query, at batch 1
+                fork.select_branch(b)
+                n = ids[b].shape[1]
+                p = torch.arange(base_len, base_len + n, device=self.device).unsqueeze(0)
+                logits = self.model(ids[b], past_key_values=fork, use_cache=True, position_ids=p).logits[:, -1]
+                pos[b] = base_len + n
+                take(b, self.next_token(logits, self.gen_kwargs, self.sample_generator))
         while any(live):    # one token for every live branch per step
             logits = self.model(cur, past_key_values=fork, use_cache=True, position_ids=pos).logits[:, -1]
             pos += 1
