@@ -101,6 +101,13 @@ PREFILL_SIGNATURES = {
                                    _i, _i, _f, _i, _vp, _sz, _vp]),
 }
 
+# the entry points of include/kvzip_hip_multi_prefill.h (the packed first step over several independent pruned caches), bound by load()
+MULTI_PREFILL_SIGNATURES = {
+    "kvz_multi_prefill_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "kvz_multi_prefill": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i,
+                               _f, _i, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -127,7 +134,7 @@ def load() -> C.CDLL:
         fn.restype = res
         fn.argtypes = args
     for header, table in (("kvzip_hip_tighten.h", EXT_SIGNATURES), ("kvzip_hip_multi.h", MULTI_SIGNATURES),
-                          ("kvzip_hip_prefill.h", PREFILL_SIGNATURES)):
+                          ("kvzip_hip_prefill.h", PREFILL_SIGNATURES), ("kvzip_hip_multi_prefill.h", MULTI_PREFILL_SIGNATURES)):
         for name, (res, args) in table.items():
             fn = getattr(lib, name, None)
             if fn is None:   # (a library built before the header existed: same ABI version, so say what to do)

@@ -7,7 +7,7 @@ interface registry).  Hooks on the cache object, in this order (attention/attn.p
     prepare()+attend()  variable-length attention over the pruned KV   (if cache.pruned)
     update_attend()     the three of them in one launch                (generation step on a pruned slack-layout cache)
     first_step() / update_attend() of a ForkedCache                    (several queries decoding over one shared pruned cache)
-    update_attend() of a CacheBatch                                    (several independent pruned caches decoding together)
+    first_step() / update_attend() of a CacheBatch                     (several independent pruned caches decoding together)
 
 The dense (pre-prune) attention — flash-attn's dense kernel in the reference (attention/attn.py:75-89) — runs on the
 library's multi-row kernel (``ops.flash_fwd`` -> ``kvz_flash_fwd``), registered as the attention implementation
@@ -81,6 +81,12 @@ def llama_qwen_attn_forward(self, hidden_states: torch.Tensor,
         return self.o_proj(attn_output), None
     # batched decode (kvcache.CacheBatch): one token for each of B independent pruned caches; the other place a batch > 1 is taken
     if getattr(kv, "layout", None) == "multi":
+        if bsz == 1 and getattr(kv, "_packed", None) is not None:
+            # packed first step: the query tokens of the selected caches back to back in one batch-1 pass
+            n_kv = self.config.num_key_value_heads
+            attn = kv.first_step(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling)     # [Hkv, q, G, D]
+            attn_output = attn.view(bsz, n_kv, q_len, -1, self.head_dim).transpose(1, 2).reshape(bsz, q_len, -1).contiguous()
+            return self.o_proj(attn_output), None
         if not (q_len == 1 and bsz == kv.n_caches):
             from . import ops
             raise ops.KvzError(f"cache batch: a forward pass over a CacheBatch is one decode step of its {kv.n_caches} caches (got batch "

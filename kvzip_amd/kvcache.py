@@ -813,8 +813,12 @@ class CacheBatch:
     makes the batch rebuild its segment table (host arrays of addresses, starts and lengths; no tensor of a member is held between
     calls).  Offsets may differ between members and between calls.
 
-    Hook for the attention adapter (``kvzip_amd.attn``): ``update_attend`` - ``[B, H, 1, D]`` queries, one new token per live member.
-    First steps (``q_len > 1``) do not go through the batch: they run at batch 1 on each member's own path."""
+    Hooks for the attention adapter (``kvzip_amd.attn``):
+      * ``update_attend`` - ``[B, H, 1, D]`` queries, one new token per live member;
+      * ``first_step`` - after ``select_packed``: the query tokens of several members back to back in ONE batch-1 pass
+        (``kvz_multi_prefill``: one split and one combine launch per layer whatever the number of members), every member ending up
+        exactly as after its own ``update`` + ``prepare`` + ``attend``.
+    Without a packing, first steps (``q_len > 1``) do not go through the batch: they run at batch 1 on each member's own path."""
 
     def __init__(self, caches):
         caches = list(caches)
@@ -853,13 +857,96 @@ class CacheBatch:
         self._tables: Optional[List[ops.MultiTable]] = None   # per layer; valid while the members' layout epochs are _epochs
         self._epochs: Optional[Tuple[int, ...]] = None
         self._ws = None
+        self._packed: Optional[Tuple[List[int], List[int]]] = None   # (members, lengths) of the next forward pass (select_packed)
+        self._ptables = None                                  # the tables in packing order, valid for _pkey = (epochs, order)
+        self._pkey = None
+        self._pws = None
 
     def get_seq_length(self, layer_idx: Optional[int] = 0) -> int:
         return max(c.get_seq_length(layer_idx) for c in self.caches)
 
+    def select_packed(self, members: Sequence[int], lengths: Sequence[int]) -> None:
+        """The next forward pass carries the queries of ``members`` (distinct, live) back to back, ``lengths[i]`` tokens of
+        ``members[i]`` each: every layer's ``first_step`` then takes ``sum(lengths)`` positions.  Cleared after the last layer's call."""
+        members, lengths = [int(b) for b in members], [int(n) for n in lengths]
+        if len(members) != len(lengths):
+            raise ops.KvzError(f"cache batch: select_packed got {len(members)} members and {len(lengths)} lengths")
+        if not members:
+            raise ops.KvzError("cache batch: select_packed needs at least one member")
+        if len(set(members)) != len(members):
+            raise ops.KvzError(f"cache batch: select_packed names a member twice ({members}): its rows would land in one slack twice")
+        for b, n in zip(members, lengths):
+            if not 0 <= b < self.n_caches:
+                raise ops.KvzError(f"cache batch: select_packed: no member {b} (the batch has {self.n_caches})")
+            if not self.active[b]:
+                raise ops.KvzError(f"cache batch: select_packed: member {b} is retired")
+            if n < 0:
+                raise ops.KvzError(f"cache batch: select_packed: member {b} has a negative length {n}")
+        self._packed = (members, lengths)
+
     def retire(self, b: int) -> None:
         """Member ``b`` is finished (EOS, token budget): later steps skip it (no write, no work item, zero output rows)."""
         self.active[b] = False
+
+    def _packed_table(self, layer_idx: int, order: List[int]) -> "ops.MultiTable":
+        """The layer's table with the members in ``order`` (the runs of a packing lie in the order it names its members)."""
+        key = (tuple(c._layout_epoch for c in self.caches), tuple(order))
+        if self._ptables is None or key != self._pkey:
+            Hkv = self.n_heads_kv
+            cs = [self.caches[b] for b in order]
+            metas = [c.info["meta_host"] for c in cs]
+            self._ptables = [ops.MultiTable([c.key_cache[l] for c in cs], [c.value_cache[l] for c in cs],
+                                            [list(m[l][:Hkv]) for m in metas], [list(m[l][Hkv:2 * Hkv]) for m in metas],
+                                            [c.slack for c in cs]) for l in range(self.n_layers)]
+            self._pkey = key
+        return self._ptables[layer_idx]
+
+    def first_step(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
+                   softmax_scale: Optional[float] = None) -> torch.Tensor:
+        """The packed first step of the selected members (``select_packed``): query ``[1, H, T, D]``, key / value ``[1, Hkv, T, D]``
+        with ``T = sum(lengths)``, the members' query tokens back to back.  Every member's rows go to its own slack and see only its
+        own segments and its own run (bottom-right causal); returns ``[Hkv, T, G, D]``.  Afterwards every member with positions is
+        exactly as after its own ``update`` + ``prepare`` + ``attend`` with ``q_len = lengths[i]``."""
+        if self._packed is None:
+            raise ops.KvzError("cache batch: first_step needs a packing (select_packed): without one, first steps run at batch 1 on "
+                               "each cache's own path")
+        members, lengths = self._packed
+        bsz, _, T, D = query_states.shape
+        if bsz != 1 or T != sum(lengths):
+            raise ops.KvzError(f"cache batch: the packed first step takes [1, H, {sum(lengths)}, D] queries, the lengths "
+                               f"{lengths} of members {members} back to back (got batch {bsz}, {T} positions)")
+        for b, n in zip(members, lengths):
+            c = self.caches[b]
+            if not (c.pruned and c.info.get("flatten") and c.layout == "slack"):
+                raise ops.KvzError("cache batch: a member is no longer a pruned slack-layout cache")
+        offsets = []
+        for b, n in zip(members, lengths):
+            c = self.caches[b]
+            off = c.info["offset"][layer_idx]
+            if n and off + n > c.slack:
+                c._grow_slack(off + n)      # (bumps the member's layout epoch: the table below is rebuilt)
+            offsets.append(off)
+        # the runs of positions in packing order, then the members that take no part (empty runs at the end)
+        order = members + [b for b in range(self.n_caches) if b not in members]
+        cu = [0]
+        for n in lengths:
+            cu.append(cu[-1] + n)
+        cu += [T] * (self.n_caches - len(members))
+        offsets += [0] * (self.n_caches - len(members))
+        table = self._packed_table(layer_idx, order)
+        if self._pws is None or self._pws[0] != (T, D):
+            self._pws = ((T, D), ops.multi_prefill_workspace(T, self.n_caches, self.n_heads_kv, self.n_group_kv, D, self.device))
+        out = ops.multi_prefill(query_states, cu, table, offsets, key_states, value_states, softmax_scale=softmax_scale,
+                                workspace=self._pws[1])
+        for b, n, off in zip(members, lengths, offsets):
+            if n:
+                c = self.caches[b]
+                c.info["offset"][layer_idx] = off + n
+                if layer_idx == 0:
+                    c._seen_tokens += n
+        if layer_idx == self.n_layers - 1:
+            self._packed = None
+        return out
 
     def _table(self, layer_idx: int) -> "ops.MultiTable":
         epochs = tuple(c._layout_epoch for c in self.caches)

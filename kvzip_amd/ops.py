@@ -702,6 +702,59 @@ def multi_attn_append(q: torch.Tensor, table: MultiTable, offsets: Sequence[int]
     return out
 
 
+def multi_prefill_workspace(T: int, B: int, Hkv: int, G: int, D: int, device) -> torch.Tensor:
+    """Scratch of ``multi_prefill`` for T packed positions (partials of the work items); no initialisation needed, no dependence on
+    the key lengths."""
+    need = _lib.load().kvz_multi_prefill_workspace_bytes(T, B, Hkv, G, D)
+    return torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+
+
+def multi_prefill(query: torch.Tensor, cu_q: Sequence[int], table: MultiTable, offsets: Sequence[int], k_new: torch.Tensor,
+                  v_new: torch.Tensor, softmax_scale: Optional[float] = None, workspace: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The PACKED first step of B independent caches (``kvz_multi_prefill``, include/kvzip_hip_multi_prefill.h): their queries back
+    to back, cache b owning positions ``cu_q[b] : cu_q[b + 1]`` (host list of B + 1, ``cu_q[0] = 0``; a cache without positions takes
+    no part: nothing of it is read or written).  query ``[1, H, T, D]``, k_new / v_new ``[1, Hkv, T, D]`` (any head / position
+    stride, rows contiguous); ``table`` the caches' segments; ``offsets[b]`` rows appended to cache b before this call.  Writes every
+    cache's new rows to rows ``seg_start + len + offset ...`` of its head segments, attends every position over its own cache's
+    segment and its own run up to itself, and returns ``[Hkv, T, G, D]``."""
+    import ctypes as C
+    lib = _lib.load()
+    b1, H, T, D = query.shape
+    B, Hkv = table.B, table.Hkv
+    G = H // Hkv
+    assert b1 == 1 and G * Hkv == H and len(cu_q) == B + 1 and len(offsets) == B
+    assert table.D == D and table.dtype == query.dtype
+    assert k_new.shape == (1, Hkv, T, D) and v_new.shape == (1, Hkv, T, D)
+    if int(cu_q[B]) != T:
+        raise KvzError(f"multi_prefill: cu_q ends at {int(cu_q[B])}, the packed query holds {T} positions")
+    if query.stride(-1) != 1 or query.stride(1) % 8 or query.stride(2) % 8:
+        query = query.contiguous()
+    if k_new.stride(-1) != 1 or k_new.stride(1) % 8 or k_new.stride(2) % 8:
+        k_new = k_new.contiguous()
+    if v_new.stride(-1) != 1 or v_new.stride(1) % 8 or v_new.stride(2) % 8:
+        v_new = v_new.contiguous()
+    _same_device(query, k_new, v_new, workspace, out)
+    if query.device != table.device:
+        raise KvzError(f"all tensors of a call must live on one device (got {query.device} and the caches on {table.device})")
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty((Hkv, T, G, D), dtype=query.dtype, device=query.device)
+    assert out.shape == (Hkv, T, G, D) and out.is_contiguous() and out.dtype == query.dtype
+    if T == 0:   # (nothing packed: nothing to launch - and an empty tensor has no address to hand over)
+        return out
+    if workspace is None:
+        workspace = multi_prefill_workspace(T, B, Hkv, G, D, query.device)
+    cu = (C.c_int32 * (B + 1))(*[int(x) for x in cu_q])
+    off = (C.c_int32 * B)(*[int(x) for x in offsets])
+    rc = lib.kvz_multi_prefill(query.data_ptr(), G * query.stride(1), query.stride(1), query.stride(2), cu, table.k_ptrs, table.v_ptrs,
+                               table.seg, table.lens, table.slack, off, k_new.data_ptr(), v_new.data_ptr(), k_new.stride(1),
+                               k_new.stride(2), v_new.stride(1), v_new.stride(2), B, Hkv, G, D, float(scale),
+                               _dtype_code(query.dtype), out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(query))
+    check(rc, "kvz_multi_prefill")
+    return out
+
+
 def flash_fwd_ragged(query: torch.Tensor, k_flat: torch.Tensor, v_flat: torch.Tensor, starts: Sequence[int], lens: Sequence[int],
                      causal: bool, softmax_scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The ragged form of ``flash_fwd``: query ``[1, H, q, D]`` over flat K, V ``[rows, D]`` in which KV head h owns rows

@@ -125,6 +125,7 @@ class ModelKVzip:
         # generate_batch: the first steps of all branches of a wave as ONE packed forward pass (kvcache.ForkedCache.select_packed:
         # the shared context and the model's weights are read once per wave instead of once per query); False: one forward per branch
         self.fork_packed_first = True
+        self.multi_packed_first = True   # generate_multi: the first steps of a wave as ONE packed forward pass (CacheBatch.first_step)
         self.multi_max_caches = 16   # caches of one batched decode wave (generate_multi), besides the kernel's own limit of 128 // Hkv
         self.sample_generator: Optional[torch.Generator] = None   # seed source of do_sample=True (None: torch's global generator)
         self.sys_prompt_ids = torch.zeros((1, 0), dtype=torch.long, device=self.device)
@@ -393,7 +394,8 @@ class ModelKVzip:
     def generate_multi(self, queries, kvs, update_cache: bool = False, return_ids: bool = False) -> list:
         """Responses to one query PER CACHE, decoded together (no reference counterpart: batch is 1 there): ``queries[i]`` is
         answered over ``kvs[i]``, a pruned slack-layout ``EvictCache`` of its own - several users, each with an own compressed
-        context.  Every query's first step (its tokens) runs at batch 1 on its own cache through the path ``generate`` takes; then
+        context.  The first steps (the query tokens) of all sequences of a wave run as ONE packed forward pass over their caches
+        (``multi_packed_first``, the default; ``False``: one forward per cache at batch 1 through the path ``generate`` takes); then
         all live sequences decode in one batch, one token each per step, whose attention is one launch per layer over all the caches
         (``kvcache.CacheBatch``) and whose other layers read the model's weights once for the whole batch.  Same knobs as ``generate``
         (``gen_kwargs``; the last token of every answer is dropped as there); a sequence stops at EOS or ``max_new_tokens`` while the
@@ -410,6 +412,13 @@ class ModelKVzip:
         for w0 in range(0, len(ids), wave):
             answers += self._generate_multi_wave(ids[w0:w0 + wave], kvs[w0:w0 + wave], update_cache)
         return answers if return_ids else [self.decode(a) for a in answers]
+
+    def _packs_first_steps_multi(self, lengths: List[int]) -> bool:
+        """Whether a wave of queries of these lengths (one per cache) takes the packed first step.  Every wave of two or more does;
+        a shape rule - should a measurement show a shape at which one pass per cache is faster - goes HERE
+        (tools/multi_prefill_bench.py).  (An empty query has no last position to take a token from: it goes to the
+        per-cache loop, which fails on it as it always did.)"""
+        return bool(self.multi_packed_first) and len(lengths) >= 2 and all(n > 0 for n in lengths)
 
     def _generate_multi_wave(self, ids: List[torch.Tensor], kvs: list, update_cache: bool) -> List[torch.Tensor]:
         B = len(ids)
@@ -431,10 +440,23 @@ class ModelKVzip:
                 live[b] = False
                 batch.retire(b)
 
-        for b in range(B):  # first step of every sequence: its query on its own cache, at batch 1
-            logits = self.model(ids[b], past_key_values=kvs[b], use_cache=True).logits[:, -1]
-            pos[b] = kvs[b].get_seq_length()          # (the caches have different lengths: explicit positions from here on)
-            take(b, self.next_token(logits, self.gen_kwargs, self.sample_generator))
+        lens = [x.shape[1] for x in ids]
+        if self._packs_first_steps_multi(lens):
+            # first steps of all sequences in ONE forward pass: the queries back to back, every one at the positions behind its own cache
+            batch.select_packed(list(range(B)), lens)
+            p = torch.cat([torch.arange(kv.get_seq_length(), kv.get_seq_length() + n, device=self.device)
+                           for kv, n in zip(kvs, lens)]).unsqueeze(0)
+            logits = self.model(torch.cat(ids, dim=1), past_key_values=batch, use_cache=True, position_ids=p).logits
+            end = 0
+            for b, n in enumerate(lens):   # the next token of a sequence comes from its last packed position
+                end += n
+                pos[b] = kvs[b].get_seq_length()
+                take(b, self.next_token(logits[:, end - 1], self.gen_kwargs, self.sample_generator))
+        else:
+            for b in range(B):  # first step of every sequence: its query on its own cache, at batch 1
+                logits = self.model(ids[b], past_key_values=kvs[b], use_cache=True).logits[:, -1]
+                pos[b] = kvs[b].get_seq_length()          # (the caches have different lengths: explicit positions from here on)
+                take(b, self.next_token(logits, self.gen_kwargs, self.sample_generator))
         while any(live):    # one token for every live sequence per step
             logits = self.model(cur, past_key_values=batch, use_cache=True, position_ids=pos).logits[:, -1]
             pos += 1
