@@ -11,43 +11,13 @@
 //   S^T = K.Q^T on v_mfma_f32_16x16x32 with K rows loaded straight from HBM as the A operand (16-byte
 //   contiguous per lane, no LDS); softmax state lives in registers (lane = one query row);
 //   O^T += V^T.P^T with V staged through a per-wave padded LDS tile and read back transposed by
-//   ds_read_b64_tr_b16.  The last block of a head to finish merges the head's partials.
-#include "kvz_common.h"
-
+//   ds_read_b64_tr_b16 (types and tile constants: kvz_wave_tile.h).  A second kernel merges the head's partials.
+#include "kvz_wave_tile.h"
 
 namespace kvz {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef short s4 __attribute__((ext_vector_type(4)));
-typedef short s8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct HalfTraits;
-template <> struct HalfTraits<_Float16> {
-    typedef h8 v8;
-    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct HalfTraits<__bf16> {
-    typedef b8 v8;
-    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
 constexpr int AT_THREADS = 512;
 constexpr int AT_WAVES = 8;
-constexpr int AT_KT = 32;           // keys per wave-tile
-constexpr int AT_RT = 16;           // query rows per block (MFMA N)
-
-template <int D> struct AttnCfg {
-    static constexpr int ROW_BYTES = D * 2;
-    static constexpr int VSTRIDE = ROW_BYTES + 32;          // padded LDS row: conflict-free tr reads
-    static constexpr int WAVE_LDS = AT_KT * VSTRIDE;        // bytes of V staging per wave
-    static constexpr int KK = D / 32;                       // MFMA k-steps over the head dim
-    static constexpr int DB = D / 16;                       // 16-wide output column blocks
-    static constexpr int CPR = ROW_BYTES / 16;              // 16-byte chunks per row
-    static constexpr int VLOADS = AT_KT * CPR / WAVE;       // 16-byte V loads per lane per tile
-};
 
 // APPEND: the decode step's O(1) cache append is done by the attention kernel.  k_len_offset already counts the new token; the
 // block that owns the last key range of a head first copies the new K and V row of that head from the state tensors into
@@ -70,17 +40,15 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
     int k_len_offset, const int32_t* __restrict__ k_len_offset_dev, HeadMeta hm, int Hkv, int G, int q_len, int target_items, float scale,
     int causal, float* part_o, float* part_ml, uint32_t* counters, int n_rtiles, T* __restrict__ out, const T* __restrict__ k_new,
     const T* __restrict__ v_new, int64_t kn_head_stride, int64_t vn_head_stride) {
-    typedef AttnCfg<D> C;
-    typedef typename HalfTraits<T>::v8 v8;
+    typedef TileCfg<D> C;
+    typedef typename Half<T>::v8 v8;
     // (the part of the appended-token count that lives on the DEVICE: a captured generation step is replayed with unchanged arguments)
     if (k_len_offset_dev) k_len_offset += *k_len_offset_dev;
     auto len_of = [&](int hh) -> int { return (HOSTMETA ? hm.len[hh] : k_len[hh]) + k_len_offset; };
     // ---- this block's work item: (head, key range) from the ragged lengths (all wave-uniform scalar work) ----
     int total = 0;
     for (int hh = 0; hh < Hkv; ++hh) total += len_of(hh);
-    int chunk = (total + target_items - 1) / target_items;
-    chunk = (chunk + 127) / 128 * 128;
-    if (chunk < 128) chunk = 128;
+    const int chunk = chunk_of(total, target_items);
     int h = -1, split = 0, first_item = 0;
     {
         int b = blockIdx.x, items = 0;
@@ -119,7 +87,7 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
     char* wl = lds + wave * C::WAVE_LDS;
 
     // ---- stationary Q fragment (B operand of S^T = K.Q^T): col = query row, k = head-dim slice ----
-    const int qrow = rt * AT_RT + l15;
+    const int qrow = rt * TILE_RT + l15;
     const bool qvalid = qrow < R;
     v8 qf[C::KK];
     {
@@ -141,7 +109,7 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
     f4 o[C::DB];
 #pragma unroll
     for (int i = 0; i < C::DB; ++i) o[i] = f4{0.f, 0.f, 0.f, 0.f};
-    const float sl2 = scale * 1.44269504088896340736f;  // work in the exp2 domain
+    const float sl2 = scale * LOG2E;  // work in the exp2 domain
 
     auto load_tile = [&](u32x4 (&kr)[2][C::KK], u32x4 (&vr)[C::VLOADS], int t0) {
 #pragma unroll
@@ -169,7 +137,7 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
             s[sub] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < C::KK; ++kk)
-                s[sub] = HalfTraits<T>::mfma(__builtin_bit_cast(v8, kr[sub][kk]), qf[kk], s[sub]);
+                s[sub] = Half<T>::mfma(__builtin_bit_cast(v8, kr[sub][kk]), qf[kk], s[sub]);
         }
 #pragma unroll
         for (int it = 0; it < C::VLOADS; ++it) {
@@ -211,7 +179,7 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
             s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(trp + db * 32));
             s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(trp + 16 * C::VSTRIDE + db * 32));
             s8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            o[db] = HalfTraits<T>::mfma(__builtin_bit_cast(v8, both), pb, o[db]);
+            o[db] = Half<T>::mfma(__builtin_bit_cast(v8, both), pb, o[db]);
         }
     };
     // The wave's tiles, one requested AHEAD of the one being computed.  Round 4: the steady-state loop issues the next tile's loads
@@ -219,8 +187,8 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
     // waits that are right on both paths - s_waitcnt vmcnt(7) .. vmcnt(0) before the V rows of the CURRENT tile go to LDS - which
     // drains the tile that has just been requested in the middle of every iteration: no load was ever in flight while a wave
     // computed, and the kernel ran at 21 us where the bare read stream takes 12.5 (profiles/r4_probe_stream.txt).
-    const int t_first = c0 + wave * AT_KT;
-    constexpr int T_STEP = AT_WAVES * AT_KT;
+    const int t_first = c0 + wave * TILE_KT;
+    constexpr int T_STEP = AT_WAVES * TILE_KT;
     if (t_first < c1) {
         load_tile(kraw, vraw, t_first);
         int t0 = t_first;
@@ -246,10 +214,10 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
     // the padded row puts the 16-byte stores of 8 consecutive query rows on 8 different bank groups.  Only valid query rows are
     // written and merged (decode: G of the 16).
     constexpr int WSTR = D + 4;                          // floats per staged row
-    static_assert((AT_RT * WSTR + 2 * AT_RT) * 4 <= C::WAVE_LDS, "the wave's V tile holds its merge staging");
+    static_assert((TILE_RT * WSTR + 2 * TILE_RT) * 4 <= C::WAVE_LDS, "the wave's V tile holds its merge staging");
     float* wo = reinterpret_cast<float*>(wl);            // [16 q][D + 4]
-    float* wm = wo + AT_RT * WSTR;                       // [16] m, [16] l
-    const int rows_valid = min(AT_RT, R - rt * AT_RT);
+    float* wm = wo + TILE_RT * WSTR;                       // [16] m, [16] l
+    const int rows_valid = min(TILE_RT, R - rt * TILE_RT);
     if (l15 < rows_valid) {
 #pragma unroll
         for (int db = 0; db < C::DB; ++db) *reinterpret_cast<f4*>(wo + l15 * WSTR + db * 16 + quad * 4) = o[db];
@@ -257,13 +225,13 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
     }
     __syncthreads();
 
-    const int64_t pbase = ((int64_t)(first_item + split) * n_rtiles + rt) * AT_RT;  // partial slot of this item
+    const int64_t pbase = ((int64_t)(first_item + split) * n_rtiles + rt) * TILE_RT;  // partial slot of this item
     for (int e = threadIdx.x; e < rows_valid * (D / 4); e += AT_THREADS) {
         const int qq = e / (D / 4), d = (e % (D / 4)) * 4;
         float mw[AT_WAVES], M = -INFINITY;
 #pragma unroll
         for (int w = 0; w < AT_WAVES; ++w) {
-            mw[w] = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS)[AT_RT * WSTR + qq];
+            mw[w] = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS)[TILE_RT * WSTR + qq];
             M = fmaxf(M, mw[w]);
         }
         f4 acc4 = f4{0.f, 0.f, 0.f, 0.f};
@@ -274,7 +242,7 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
             const float wgt = (mw[w] == -INFINITY) ? 0.f : exp2f(mw[w] - M);
             const f4 ov = *reinterpret_cast<const f4*>(pw + qq * WSTR + d);
             acc4[0] += wgt * ov[0]; acc4[1] += wgt * ov[1]; acc4[2] += wgt * ov[2]; acc4[3] += wgt * ov[3];
-            lsum += wgt * pw[AT_RT * WSTR + 16 + qq];
+            lsum += wgt * pw[TILE_RT * WSTR + 16 + qq];
         }
         *reinterpret_cast<f4*>(part_o + (pbase + qq) * D + d) = acc4;
         if (d == 0) *reinterpret_cast<float2*>(part_ml + (pbase + qq) * 2) = make_float2(M, lsum);
@@ -295,18 +263,16 @@ __global__ __launch_bounds__(CB_THREADS) void varlen_attn_combine2_kernel(const 
     if (k_len_offset_dev) k_len_offset += *k_len_offset_dev;
     const int h = blockIdx.x, rt = blockIdx.y, qq = blockIdx.z;
     const int R = q_len * G;
-    if (rt * AT_RT + qq >= R) return;
+    if (rt * TILE_RT + qq >= R) return;
     auto len_of = [&](int hh) -> int { return (HOSTMETA ? hm.len[hh] : k_len[hh]) + k_len_offset; };
     int total = 0;
     for (int hh = 0; hh < Hkv; ++hh) total += len_of(hh);
-    int chunk = (total + target_items - 1) / target_items;
-    chunk = (chunk + 127) / 128 * 128;
-    if (chunk < 128) chunk = 128;
+    const int chunk = chunk_of(total, target_items);
     int first_item = 0;
     for (int hh = 0; hh < h; ++hh) first_item += max(1, (len_of(hh) + chunk - 1) / chunk);
     const int nsp = max(1, (len_of(h) + chunk - 1) / chunk);
-    const int64_t base = ((int64_t)first_item * n_rtiles + rt) * AT_RT + qq;  // + s * n_rtiles * AT_RT
-    const int64_t istride = (int64_t)n_rtiles * AT_RT;
+    const int64_t base = ((int64_t)first_item * n_rtiles + rt) * TILE_RT + qq;  // + s * n_rtiles * TILE_RT
+    const int64_t istride = (int64_t)n_rtiles * TILE_RT;
     const int tid = threadIdx.x;
     const int d = tid % D, slice = tid / D;
 
@@ -352,7 +318,7 @@ __global__ __launch_bounds__(CB_THREADS) void varlen_attn_combine2_kernel(const 
             float a = 0.f, l = 0.f;
 #pragma unroll
             for (int sl = 0; sl < SLICES; ++sl) { a += s_acc[sl][tid]; l += s_red[sl]; }
-            out[((int64_t)h * R + rt * AT_RT + qq) * D + tid] = (T)((l > 0.f) ? a / l : 0.f);
+            out[((int64_t)h * R + rt * TILE_RT + qq) * D + tid] = (T)((l > 0.f) ? a / l : 0.f);
         }
         return;
     }
@@ -400,34 +366,23 @@ __global__ __launch_bounds__(CB_THREADS) void varlen_attn_combine2_kernel(const 
 #pragma unroll
         for (int sl = 0; sl < SLICES; ++sl) a += s_acc[sl][tid];
         const float l = s_L;
-        out[((int64_t)h * R + rt * AT_RT + qq) * D + tid] = (T)((l > 0.f) ? a / l : 0.f);
+        out[((int64_t)h * R + rt * TILE_RT + qq) * D + tid] = (T)((l > 0.f) ? a / l : 0.f);
     }
 }
 
 __global__ void add_i32_kernel(int32_t* p, int delta) { *p += delta; }
 
-// work items a decode call is cut into.  Default (knob 0): CUs - Hkv (256 - Hkv on MI355X), the most that can never exceed one block per CU (every head
-// rounds its item count up, so a call has at most target + Hkv items; one item beyond 256 costs a second round of blocks: 25 -> 34 us
-// per layer, profiles/r4_decode_cold_probe.txt).  Round 2 had settled on 192 with a probe whose single 80-MB cache lived in the
-// infinity cache; streaming a whole model's caches from cold HBM, 252 items are 3 % faster than 192.
-static inline int attn_items(int Hkv) {
-    const int t = tunable(TUNE_ATTN_ITEMS);
-    if (t > 0) return t;
-    const int cus = device_cus();
-    return Hkv < cus * 3 / 4 ? cus - Hkv : cus / 4;
-}
-static inline size_t align256a(size_t x) { return (x + 255) & ~(size_t)255; }
 struct AttnWs { uint32_t* counters; float* part_ml; float* part_o; size_t bytes; };
 static inline AttnWs attn_ws(void* ws, int Hkv, int n_rtiles, int D) {
-    const size_t items = (size_t)attn_items(Hkv) + Hkv;
+    const size_t items = (size_t)target_items(Hkv) + Hkv;
     AttnWs w;
     char* p = reinterpret_cast<char*>(ws);
     w.counters = reinterpret_cast<uint32_t*>(p);
-    p += align256a((size_t)Hkv * n_rtiles * sizeof(uint32_t));
+    p += align256((size_t)Hkv * n_rtiles * sizeof(uint32_t));
     w.part_ml = reinterpret_cast<float*>(p);
-    p += align256a(items * n_rtiles * AT_RT * 2 * sizeof(float));
+    p += align256(items * n_rtiles * TILE_RT * 2 * sizeof(float));
     w.part_o = reinterpret_cast<float*>(p);
-    p += align256a(items * n_rtiles * AT_RT * D * sizeof(float));
+    p += align256(items * n_rtiles * TILE_RT * D * sizeof(float));
     w.bytes = (size_t)(p - reinterpret_cast<char*>(ws));
     return w;
 }
@@ -437,9 +392,9 @@ static int launch_attn(const void* q, const void* k, const void* v, const int32_
                        int k_len_offset, const int32_t* off_dev, const int32_t* meta_host, int Hkv, int G, int q_len, float scale, int causal, void* out,
                        void* ws, hipStream_t stream, const void* k_new = nullptr, const void* v_new = nullptr,
                        int64_t kn_stride = 0, int64_t vn_stride = 0) {
-    const int n_rtiles = (q_len * G + AT_RT - 1) / AT_RT;
+    const int n_rtiles = (q_len * G + TILE_RT - 1) / TILE_RT;
     const AttnWs w = attn_ws(ws, Hkv, n_rtiles, D);
-    const int target = attn_items(Hkv);
+    const int target = target_items(Hkv);
     HeadMeta hm;
     const bool host = meta_host != nullptr && Hkv <= AT_MAXH;
     if (host)
@@ -455,7 +410,7 @@ static int launch_attn(const void* q, const void* k, const void* v, const int32_
     else { if (host) KVZ_ATTN_LAUNCH(false, true); else KVZ_ATTN_LAUNCH(false, false); }
 #undef KVZ_ATTN_LAUNCH
     KVZ_CHECK_LAUNCH("varlen_attn_split2_kernel");
-    const dim3 cgrid(Hkv, n_rtiles, AT_RT), cblock(CB_THREADS);
+    const dim3 cgrid(Hkv, n_rtiles, TILE_RT), cblock(CB_THREADS);
     if (host)
         hipLaunchKernelGGL((varlen_attn_combine2_kernel<T, D, true>), cgrid, cblock, 0, stream, w.part_o, w.part_ml, k_len, k_len_offset,
                            off_dev, hm, Hkv, G, q_len, target, n_rtiles, reinterpret_cast<T*>(out));
@@ -476,7 +431,7 @@ static int flash_min_rows() { return tunable(TUNE_FLASH_MIN_ROWS); }
 extern "C" size_t kvz_varlen_attn_workspace_bytes(int Hkv, int G, int q_len, int D, int max_len_k) {
     if (Hkv <= 0 || G <= 0 || q_len <= 0 || D <= 0 || max_len_k < 0) return 0;
     if (q_len * G > flash_min_rows()) return kvz_flash_workspace_bytes(Hkv, G, q_len, D) + 256;  // (never 0: callers pass a buffer)
-    const int n_rtiles = (q_len * G + AT_RT - 1) / AT_RT;
+    const int n_rtiles = (q_len * G + TILE_RT - 1) / TILE_RT;
     return attn_ws(nullptr, Hkv, n_rtiles, D).bytes;
 }
 
@@ -499,15 +454,13 @@ extern "C" int kvz_varlen_attn(const void* q, const void* k, const void* v, cons
                              q_len, D, scale, causal, dtype, out, (int64_t)q_len * G * D, D, (int64_t)G * D, nullptr, ws, ws_bytes,
                              stream_);
     }
-    KVZ_REQUIRE((q_len * G + AT_RT - 1) / AT_RT <= 65535, KVZ_EINVAL, "kvz_varlen_attn: too many query rows");
+    KVZ_REQUIRE((q_len * G + TILE_RT - 1) / TILE_RT <= 65535, KVZ_EINVAL, "kvz_varlen_attn: too many query rows");
     KVZ_REQUIRE(ws_bytes >= kvz_varlen_attn_workspace_bytes(Hkv, G, q_len, D, max_len_k), KVZ_EWORKSPACE,
                 "kvz_varlen_attn: workspace too small");
-    if (dtype == KVZ_F16) {
-        if (D == 128) return launch_attn<_Float16, 128>(q, k, v, k_start, k_len, k_len_offset, k_len_offset_dev, k_meta_host, Hkv, G, q_len, scale, causal, out, ws, stream);
-        return launch_attn<_Float16, 64>(q, k, v, k_start, k_len, k_len_offset, k_len_offset_dev, k_meta_host, Hkv, G, q_len, scale, causal, out, ws, stream);
-    }
-    if (D == 128) return launch_attn<__bf16, 128>(q, k, v, k_start, k_len, k_len_offset, k_len_offset_dev, k_meta_host, Hkv, G, q_len, scale, causal, out, ws, stream);
-    return launch_attn<__bf16, 64>(q, k, v, k_start, k_len, k_len_offset, k_len_offset_dev, k_meta_host, Hkv, G, q_len, scale, causal, out, ws, stream);
+#define KVZ_ATTN_CALL(T, DD) \
+    return launch_attn<T, DD>(q, k, v, k_start, k_len, k_len_offset, k_len_offset_dev, k_meta_host, Hkv, G, q_len, scale, causal, out, ws, stream)
+    KVZ_DISPATCH_HALF_D(dtype, D, KVZ_ATTN_CALL);
+#undef KVZ_ATTN_CALL
 }
 
 extern "C" int kvz_varlen_attn_append(const void* q, void* k_cache, void* v_cache, const void* k_state, const void* v_state,
@@ -528,12 +481,11 @@ extern "C" int kvz_varlen_attn_append(const void* q, void* k_cache, void* v_cach
     KVZ_REQUIRE(ws_bytes >= kvz_varlen_attn_workspace_bytes(Hkv, G, 1, D, max_len_k), KVZ_EWORKSPACE,
                 "kvz_varlen_attn_append: workspace too small");
     const int off = k_len_offset + 1;  // the keys attended to include the token appended by this call
-    if (dtype == KVZ_F16) {
-        if (D == 128) return launch_attn<_Float16, 128>(q, k_cache, v_cache, k_start, k_len, off, k_len_offset_dev, k_meta_host, Hkv, G, 1, scale, 1, out, ws, stream, k_state, v_state, k_state_head_stride, v_state_head_stride);
-        return launch_attn<_Float16, 64>(q, k_cache, v_cache, k_start, k_len, off, k_len_offset_dev, k_meta_host, Hkv, G, 1, scale, 1, out, ws, stream, k_state, v_state, k_state_head_stride, v_state_head_stride);
-    }
-    if (D == 128) return launch_attn<__bf16, 128>(q, k_cache, v_cache, k_start, k_len, off, k_len_offset_dev, k_meta_host, Hkv, G, 1, scale, 1, out, ws, stream, k_state, v_state, k_state_head_stride, v_state_head_stride);
-    return launch_attn<__bf16, 64>(q, k_cache, v_cache, k_start, k_len, off, k_len_offset_dev, k_meta_host, Hkv, G, 1, scale, 1, out, ws, stream, k_state, v_state, k_state_head_stride, v_state_head_stride);
+#define KVZ_ATTN_CALL(T, DD)                                                                                                          \
+    return launch_attn<T, DD>(q, k_cache, v_cache, k_start, k_len, off, k_len_offset_dev, k_meta_host, Hkv, G, 1, scale, 1, out, ws, stream, \
+                              k_state, v_state, k_state_head_stride, v_state_head_stride)
+    KVZ_DISPATCH_HALF_D(dtype, D, KVZ_ATTN_CALL);
+#undef KVZ_ATTN_CALL
 }
 
 

@@ -19,57 +19,21 @@
 // attn_merge_lse_kernel: merges two partial attention results by their natural-log LSEs (a branch's first step: kvz_flash_fwd over the
 // shared segments, causal = 0, and over the branch's tail, causal = 1):
 //   m = max(lse1, lse2);  w_i = exp(lse_i - m);  out = fp16/bf16((w1*o1 + w2*o2) / (w1 + w2));  both -inf -> 0.
-#include "kvz_common.h"
+#include "kvz_wave_tile.h"
 
 #include <type_traits>
 
 namespace kvz {
 namespace fork {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef short s4 __attribute__((ext_vector_type(4)));
-typedef short s8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Half;
-template <> struct Half<_Float16> {
-    typedef h8 v8;
-    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Half<__bf16> {
-    typedef b8 v8;
-    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
 constexpr int FK_THREADS = 512;
 constexpr int FK_WAVES = 8;
-constexpr int FK_KT = 32;            // keys per wave tile
-constexpr int FK_RT = 16;            // query rows per row tile (MFMA N)
 constexpr int FK_MAXH = 64;
 constexpr int FK_MAXB = 16;
 constexpr int FK_MAXROWS = 64;       // B*G
 
-template <int D> struct Cfg {
-    static constexpr int ROW_BYTES = D * 2;
-    static constexpr int VSTRIDE = ROW_BYTES + 32;          // padded LDS row: conflict-free tr reads
-    static constexpr int WAVE_LDS = FK_KT * VSTRIDE;        // bytes of V staging per wave
-    static constexpr int KK = D / 32;
-    static constexpr int DB = D / 16;
-    static constexpr int CPR = ROW_BYTES / 16;
-    static constexpr int VLOADS = FK_KT * CPR / WAVE;
-};
-
 struct HeadMeta { int32_t start[FK_MAXH]; int32_t len[FK_MAXH]; };
 struct TailLens { int32_t n[FK_MAXB]; };
-
-// the key-range cut of the shared part (the same arithmetic in both kernels)
-__device__ static inline int chunk_of(int total, int target_items) {
-    int chunk = (total + target_items - 1) / target_items;
-    chunk = (chunk + 127) / 128 * 128;
-    return chunk < 128 ? 128 : chunk;
-}
 
 template <typename T, int D, int NT>
 __global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
@@ -78,13 +42,13 @@ __global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
     const T* __restrict__ k_new, const T* __restrict__ v_new, int64_t kn_bstride, int64_t kn_hstride, int64_t vn_bstride,
     int64_t vn_hstride, int B, int Hkv, int G, int target_items, float scale, float* __restrict__ part_o,
     float* __restrict__ part_ml, float* __restrict__ tail_o, float* __restrict__ tail_ml, int n_rtiles) {
-    typedef Cfg<D> C;
+    typedef TileCfg<D> C;
     typedef typename Half<T>::v8 v8;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int l15 = lane & 15, quad = lane >> 4;
     const int R = B * G;
-    const int GT = (G + FK_RT - 1) / FK_RT;   // row tiles of ONE branch (tail items)
+    const int GT = (G + TILE_RT - 1) / TILE_RT;   // row tiles of ONE branch (tail items)
     const int TG = (GT + NT - 1) / NT;        // blocks of one tail item: one unless a single branch has more than 16 * NT rows
     const int n_tail = B * Hkv * TG;
 
@@ -116,7 +80,7 @@ __global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
         kbase = reinterpret_cast<const char*>(tail_k) + row0 * C::ROW_BYTES;
         vbase = reinterpret_cast<const char*>(tail_v) + row0 * C::ROW_BYTES;
         len = t + 1; c0 = 0; c1 = len;
-        slot0 = ((int64_t)branch * Hkv + h) * GT * FK_RT;
+        slot0 = ((int64_t)branch * Hkv + h) * GT * TILE_RT;
         po = tail_o; pml = tail_ml;
     } else {
         auto len_of = [&](int hh) -> int { return (host_meta ? hm.len[hh] : k_len[hh]) + k_len_offset; };
@@ -144,13 +108,13 @@ __global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
         c1 = min(len, c0 + chunk);
         kbase = reinterpret_cast<const char*>(k) + seg * C::ROW_BYTES;
         vbase = reinterpret_cast<const char*>(v) + seg * C::ROW_BYTES;
-        slot0 = ((int64_t)(first_item + split) * n_rtiles + (int64_t)blockIdx.y * NT) * FK_RT;
+        slot0 = ((int64_t)(first_item + split) * n_rtiles + (int64_t)blockIdx.y * NT) * TILE_RT;
         po = part_o; pml = part_ml;
     }
 
     __shared__ __attribute__((aligned(16))) char lds[FK_WAVES * C::WAVE_LDS];
     char* wl = lds + wave * C::WAVE_LDS;
-    const float sl2 = scale * 1.44269504088896340736f;  // work in the exp2 domain
+    const float sl2 = scale * LOG2E;  // work in the exp2 domain
 
     {
         // ---- stationary Q fragments, one per row tile (B operand of S^T = K.Q^T): col = query row, k = head-dim slice ----
@@ -161,15 +125,15 @@ __global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
             int bq, gq, nrows;
             if (branch >= 0) {
                 const int gt = grp * NT + i;
-                bq = branch; gq = gt * FK_RT + l15;
-                nrows = G - gt * FK_RT;
+                bq = branch; gq = gt * TILE_RT + l15;
+                nrows = G - gt * TILE_RT;
             } else {
                 const int rt = (int)blockIdx.y * NT + i;
-                const int r = rt * FK_RT + l15;
+                const int r = rt * TILE_RT + l15;
                 bq = r / G; gq = r - bq * G;
-                nrows = R - rt * FK_RT;
+                nrows = R - rt * TILE_RT;
             }
-            rows_valid[i] = max(0, min(FK_RT, nrows));
+            rows_valid[i] = max(0, min(TILE_RT, nrows));
             const bool qvalid = l15 < rows_valid[i];
             const T* qp = q + (qvalid ? (((int64_t)bq * Hkv + h) * G + gq) * D : 0) + quad * 8;
 #pragma unroll
@@ -278,8 +242,8 @@ __global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
         // The wave's tiles, one requested AHEAD of the one being computed; the steady-state loop issues the next tile's loads
         // UNCONDITIONALLY and the last tile is computed after the loop (the load structure of varlen_attn_split2_kernel: its comment
         // records what the conditional form cost).
-        const int t_first = c0 + wave * FK_KT;
-        constexpr int T_STEP = FK_WAVES * FK_KT;
+        const int t_first = c0 + wave * TILE_KT;
+        constexpr int T_STEP = FK_WAVES * TILE_KT;
         if (t_first < c1) {
             load_k(kraw, t_first);
             load_v(vraw, t_first);
@@ -305,9 +269,9 @@ __global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
 
         // ---- merge the 8 waves of the block through LDS, one row tile after the other (each wave stages in its own V tile) ----
         constexpr int WSTR = D + 4;                          // floats per staged row (bank-conflict-free, see kvz_attn.hip)
-        static_assert((FK_RT * WSTR + 2 * FK_RT) * 4 <= C::WAVE_LDS, "the wave's V tile holds its merge staging");
+        static_assert((TILE_RT * WSTR + 2 * TILE_RT) * 4 <= C::WAVE_LDS, "the wave's V tile holds its merge staging");
         float* wo = reinterpret_cast<float*>(wl);            // [16 q][D + 4]
-        float* wm = wo + FK_RT * WSTR;                       // [16] m, [16] l
+        float* wm = wo + TILE_RT * WSTR;                       // [16] m, [16] l
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
             float lr = l_run[i];
@@ -320,13 +284,13 @@ __global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
                 if (quad == 0) { wm[l15] = m_run[i]; wm[16 + l15] = lr; }
             }
             __syncthreads();
-            const int64_t pbase = slot0 + (int64_t)(grp * NT + i) * FK_RT;
+            const int64_t pbase = slot0 + (int64_t)(grp * NT + i) * TILE_RT;
             for (int e = threadIdx.x; e < rv * (D / 4); e += FK_THREADS) {
                 const int qq = e / (D / 4), d = (e % (D / 4)) * 4;
                 float mw[FK_WAVES], M = -INFINITY;
 #pragma unroll
                 for (int w = 0; w < FK_WAVES; ++w) {
-                    mw[w] = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS)[FK_RT * WSTR + qq];
+                    mw[w] = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS)[TILE_RT * WSTR + qq];
                     M = fmaxf(M, mw[w]);
                 }
                 f4 acc4 = f4{0.f, 0.f, 0.f, 0.f};
@@ -337,7 +301,7 @@ __global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
                     const float wgt = (mw[w] == -INFINITY) ? 0.f : exp2f(mw[w] - M);
                     const f4 ov = *reinterpret_cast<const f4*>(pw + qq * WSTR + d);
                     acc4[0] += wgt * ov[0]; acc4[1] += wgt * ov[1]; acc4[2] += wgt * ov[2]; acc4[3] += wgt * ov[3];
-                    lsum += wgt * pw[FK_RT * WSTR + 16 + qq];
+                    lsum += wgt * pw[TILE_RT * WSTR + 16 + qq];
                 }
                 *reinterpret_cast<f4*>(po + (pbase + qq) * D + d) = acc4;
                 if (d == 0) *reinterpret_cast<float2*>(pml + (pbase + qq) * 2) = make_float2(M, lsum);
@@ -373,10 +337,10 @@ __global__ __launch_bounds__(CB_THREADS) void fork_combine_kernel(const float* _
     for (int hh = 0; hh < h; ++hh) first_item += max(1, (len_of(hh) + chunk - 1) / chunk);
     const int nsp = max(1, (len_of(h) + chunk - 1) / chunk);
     const int r = b * G + g;
-    const int64_t base = ((int64_t)first_item * n_rtiles + r / FK_RT) * FK_RT + r % FK_RT;
-    const int64_t istride = (int64_t)n_rtiles * FK_RT;
-    const int GT = (G + FK_RT - 1) / FK_RT;
-    const int64_t trow = (((int64_t)b * Hkv + h) * GT + g / FK_RT) * FK_RT + g % FK_RT;
+    const int64_t base = ((int64_t)first_item * n_rtiles + r / TILE_RT) * TILE_RT + r % TILE_RT;
+    const int64_t istride = (int64_t)n_rtiles * TILE_RT;
+    const int GT = (G + TILE_RT - 1) / TILE_RT;
+    const int64_t trow = (((int64_t)b * Hkv + h) * GT + g / TILE_RT) * TILE_RT + g % TILE_RT;
     const int n = nsp + 1;  // the key ranges of the head, then the branch's tail (an active branch has at least its new row)
     auto ml_ptr = [&](int s2) -> const float* { return s2 < nsp ? part_ml + (base + s2 * istride) * 2 : tail_ml + trow * 2; };
     auto o_ptr = [&](int s2) -> const float* { return s2 < nsp ? part_o + (base + s2 * istride) * D : tail_o + trow * D; };
@@ -471,30 +435,25 @@ __global__ __launch_bounds__(256) void attn_merge_lse_kernel(const T* o1, const 
 
 // work items of the shared part: the decode kernel's count (one block per CU) less the tail items of the same launch
 static inline int fork_items(int B, int Hkv) {
-    int t = tunable(TUNE_ATTN_ITEMS);
-    if (t <= 0) {
-        const int cus = device_cus();
-        t = Hkv < cus * 3 / 4 ? cus - Hkv : cus / 4;
-    }
+    const int t = target_items(Hkv);
     const int floor_items = device_cus() / 4;
     return t - B * Hkv > floor_items ? t - B * Hkv : (t < floor_items ? t : floor_items);
 }
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct ForkWs { float* part_ml; float* part_o; float* tail_ml; float* tail_o; size_t bytes; };
 static inline ForkWs fork_ws(void* ws, int B, int Hkv, int G, int D) {
-    const int n_rtiles = (B * G + FK_RT - 1) / FK_RT;
-    const int GT = (G + FK_RT - 1) / FK_RT;
+    const int n_rtiles = (B * G + TILE_RT - 1) / TILE_RT;
+    const int GT = (G + TILE_RT - 1) / TILE_RT;
     // (sized for the largest item count any B gives: a workspace made once serves every wave of branches)
     int t = tunable(TUNE_ATTN_ITEMS);
     if (t <= 0) t = device_cus();
     const size_t items = (size_t)t + Hkv;
-    const size_t trows = (size_t)B * Hkv * GT * FK_RT;
+    const size_t trows = (size_t)B * Hkv * GT * TILE_RT;
     ForkWs w;
     char* p = reinterpret_cast<char*>(ws);
     w.part_ml = reinterpret_cast<float*>(p);
-    p += align256(items * n_rtiles * FK_RT * 2 * sizeof(float));
+    p += align256(items * n_rtiles * TILE_RT * 2 * sizeof(float));
     w.part_o = reinterpret_cast<float*>(p);
-    p += align256(items * n_rtiles * FK_RT * D * sizeof(float));
+    p += align256(items * n_rtiles * TILE_RT * D * sizeof(float));
     w.tail_ml = reinterpret_cast<float*>(p);
     p += align256(trows * 2 * sizeof(float));
     w.tail_o = reinterpret_cast<float*>(p);
@@ -520,7 +479,7 @@ static int launch_fork(const void* q, const void* k, const void* v, const int32_
                        const int32_t* meta_host, void* tail_k, void* tail_v, int tail_cap, const int32_t* tail_len, const void* k_new,
                        const void* v_new, int64_t kn_b, int64_t kn_h, int64_t vn_b, int64_t vn_h, int B, int Hkv, int G, float scale,
                        void* out, void* ws, hipStream_t stream) {
-    const int n_rtiles = (B * G + FK_RT - 1) / FK_RT;
+    const int n_rtiles = (B * G + TILE_RT - 1) / TILE_RT;
     const ForkWs w = fork_ws(ws, B, Hkv, G, D);
     HeadMeta hm;
     const int host = meta_host != nullptr;
@@ -533,7 +492,7 @@ static int launch_fork(const void* q, const void* k, const void* v, const int32_
     ProfScope ps("fork_attn", stream);
     // two row tiles per block from two row tiles on; three or four row tiles are two blocks per work item (grid.y)
     const int nt = n_rtiles >= 2 ? 2 : 1;
-    const int GT = (G + FK_RT - 1) / FK_RT, TG = (GT + nt - 1) / nt;
+    const int GT = (G + TILE_RT - 1) / TILE_RT, TG = (GT + nt - 1) / nt;
     const int target = fork_items(B * TG, Hkv);
     const dim3 grid(B * Hkv * TG + target + Hkv, (n_rtiles + nt - 1) / nt);
     if (nt == 2)
@@ -591,12 +550,9 @@ extern "C" int kvz_fork_attn_append(const void* q, const void* k_cache, const vo
     KVZ_REQUIRE(ws_bytes >= kvz_fork_attn_workspace_bytes(B, Hkv, G, D, 0), KVZ_EWORKSPACE, "kvz_fork_attn_append: workspace too small");
 #define KVZ_FORK_ARGS q, k_cache, v_cache, k_start, k_len, k_len_offset, k_meta_host, tail_k, tail_v, tail_cap, tail_len_host, k_new, v_new, \
                       k_new_batch_stride, k_new_head_stride, v_new_batch_stride, v_new_head_stride, B, Hkv, G, scale, out, ws, stream
-    if (dtype == KVZ_F16) {
-        if (D == 128) return fork::launch_fork<_Float16, 128>(KVZ_FORK_ARGS);
-        return fork::launch_fork<_Float16, 64>(KVZ_FORK_ARGS);
-    }
-    if (D == 128) return fork::launch_fork<__bf16, 128>(KVZ_FORK_ARGS);
-    return fork::launch_fork<__bf16, 64>(KVZ_FORK_ARGS);
+#define KVZ_FORK_CALL(T, DD) return fork::launch_fork<T, DD>(KVZ_FORK_ARGS)
+    KVZ_DISPATCH_HALF_D(dtype, D, KVZ_FORK_CALL);
+#undef KVZ_FORK_CALL
 #undef KVZ_FORK_ARGS
 }
 
@@ -614,8 +570,7 @@ extern "C" int kvz_attn_merge_lse(const void* o1, const float* lse1, const void*
 #define KVZ_MERGE_LAUNCH(T, DD)                                                                                                       \
     hipLaunchKernelGGL((fork::attn_merge_lse_kernel<T, DD>), grid, block, 0, stream, reinterpret_cast<const T*>(o1), lse1,              \
                        reinterpret_cast<const T*>(o2), lse2, reinterpret_cast<T*>(out), rows)
-    if (dtype == KVZ_F16) { if (D == 128) KVZ_MERGE_LAUNCH(_Float16, 128); else KVZ_MERGE_LAUNCH(_Float16, 64); }
-    else { if (D == 128) KVZ_MERGE_LAUNCH(__bf16, 128); else KVZ_MERGE_LAUNCH(__bf16, 64); }
+    KVZ_DISPATCH_HALF_D(dtype, D, KVZ_MERGE_LAUNCH);
 #undef KVZ_MERGE_LAUNCH
     KVZ_CHECK_LAUNCH("attn_merge_lse_kernel");
     return KVZ_OK;

@@ -20,52 +20,18 @@
 //                        which is kvz_attn_merge_lse's formula with the tail side kept in fp32 and unnormalised (its LSE is
 //                        m + log2 l): one division, one cast.  lse_shared = -inf gives fp16/bf16(a / l), the 'div' form of the decode
 //                        combines.  Every lane loads the o_shared elements it overwrites before it writes them: out may be o_shared.
-#include "kvz_common.h"
+#include "kvz_wave_tile.h"
 
 #include "../../include/kvzip_hip_prefill.h"
 
 namespace kvz {
 namespace fprefill {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-typedef short s4 __attribute__((ext_vector_type(4)));
-typedef short s8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Half;
-template <> struct Half<_Float16> {
-    typedef h8 v8;
-    typedef h4 v4;
-    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Half<__bf16> {
-    typedef b8 v8;
-    typedef b4 v4;
-    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
 constexpr int FP_WAVES = 4;          // row tiles of one block (one wave each, one wave per SIMD)
 constexpr int FP_THREADS = FP_WAVES * WAVE;
-constexpr int FP_KT = 32;            // keys per tile
-constexpr int FP_RT = 16;            // query rows per row tile (MFMA N)
 constexpr int FP_MAXB = 16;
 constexpr int FP_MAXH = 64;
 constexpr int FP_MAXG = 64;
-
-template <int D> struct Cfg {
-    static constexpr int ROW_BYTES = D * 2;
-    static constexpr int VSTRIDE = ROW_BYTES + 32;          // padded LDS row: conflict-free tr reads (kvz_fork.hip)
-    static constexpr int WAVE_LDS = FP_KT * VSTRIDE;        // bytes of V staging per wave
-    static constexpr int KK = D / 32;
-    static constexpr int DB = D / 16;
-    static constexpr int CPR = ROW_BYTES / 16;
-    static constexpr int VLOADS = FP_KT * CPR / WAVE;
-};
 
 // the packing, by value: positions, tail index, tail length and first block of every run of positions (= branch)
 struct Table {
@@ -80,7 +46,7 @@ __global__ __launch_bounds__(FP_THREADS) void fork_prefill_kernel(
     const T* __restrict__ q, int64_t qs_head, int64_t qs_group, int64_t qs_pos, T* tail_k, T* tail_v, int tail_cap,
     const T* __restrict__ k_new, const T* __restrict__ v_new, int64_t kn_h, int64_t kn_p, int64_t vn_h, int64_t vn_p, const T* o_shared,
     const float* __restrict__ lse_shared, T* out, Table tb, int B, int Hkv, int G, int Ttot, float scale) {
-    typedef Cfg<D> C;
+    typedef TileCfg<D> C;
     typedef typename Half<T>::v8 v8;
     typedef typename Half<T>::v4 v4;
     const int lane = threadIdx.x & 63;
@@ -94,7 +60,7 @@ __global__ __launch_bounds__(FP_THREADS) void fork_prefill_kernel(
     const int n_b = tb.cu_q[b + 1] - cu0;
     const int t_b = tb.tail_len[b];
     const int R = n_b * G;                                  // query rows of the branch per KV head
-    const int ntiles = (R + FP_RT - 1) / FP_RT;
+    const int ntiles = (R + TILE_RT - 1) / TILE_RT;
     const int groups = (ntiles + FP_WAVES - 1) / FP_WAVES;
     const int idx = (int)blockIdx.x - tb.blk0[b];
     const int h = idx / groups;
@@ -124,17 +90,17 @@ __global__ __launch_bounds__(FP_THREADS) void fork_prefill_kernel(
     // ---- this wave's row tile ----
     const int tile = grp * FP_WAVES + wave;
     if (tile >= ntiles) return;                             // (wave-uniform; the kernel has no barrier)
-    const int r_l = tile * FP_RT + l15;                     // this lane's query row (a column of S^T and O^T)
+    const int r_l = tile * TILE_RT + l15;                     // this lane's query row (a column of S^T and O^T)
     const bool rvalid = r_l < R;
     const int p_l = rvalid ? r_l / G : 0;
     const int g_l = r_l - p_l * G;
     const int limit = rvalid ? t_b + p_l + 1 : 0;           // keys the row sees
-    const int r_last = min(tile * FP_RT + FP_RT - 1, R - 1);
+    const int r_last = min(tile * TILE_RT + TILE_RT - 1, R - 1);
     const int kend = t_b + r_last / G + 1;                  // keys the wave visits: the limit of its last row (>= 1)
 
     __shared__ __attribute__((aligned(16))) char lds[FP_WAVES * C::WAVE_LDS];
     char* wl = lds + wave * C::WAVE_LDS;
-    const float sl2 = scale * 1.44269504088896340736f;      // work in the exp2 domain
+    const float sl2 = scale * LOG2E;      // work in the exp2 domain
 
     // stationary Q fragment (B operand of S^T = K.Q^T): col = query row, k = head-dim slice
     v8 qf[C::KK];
@@ -230,9 +196,9 @@ __global__ __launch_bounds__(FP_THREADS) void fork_prefill_kernel(
     load_k(kraw, 0);
     load_v(vraw, 0);
 #pragma unroll 1
-    for (int t0 = 0; t0 < kend; t0 += FP_KT) {
-        load_k(knext, t0 + FP_KT);
-        load_v(vnext, t0 + FP_KT);
+    for (int t0 = 0; t0 < kend; t0 += TILE_KT) {
+        load_k(knext, t0 + TILE_KT);
+        load_v(vnext, t0 + TILE_KT);
         compute_tile(kraw, vraw, t0);
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub)
@@ -335,7 +301,7 @@ extern "C" int kvz_fork_prefill_tail(const void* q, int64_t q_stride_head, int64
         KVZ_REQUIRE(n == 0 || t + n <= tail_cap, KVZ_EINVAL,
                     "kvz_fork_prefill_tail: branch %d: tail_len %d + %lld new rows do not fit in tail_cap = %d", tbr, t, (long long)n,
                     tail_cap);
-        const int64_t tiles = (n * G + fprefill::FP_RT - 1) / fprefill::FP_RT;
+        const int64_t tiles = (n * G + TILE_RT - 1) / TILE_RT;
         tb.cu_q[b] = cu_q_host[b];
         tb.tail_of[b] = tbr;
         tb.tail_len[b] = t;
@@ -352,11 +318,8 @@ extern "C" int kvz_fork_prefill_tail(const void* q, int64_t q_stride_head, int64
 #define KVZ_FP_ARGS q, q_stride_head, q_stride_group, q_stride_pos, tail_k, tail_v, tail_cap, k_new, v_new, k_new_head_stride,         \
                     k_new_pos_stride, v_new_head_stride, v_new_pos_stride, o_shared, lse_shared, out, tb, (int)blocks, B, Hkv, G, Ttot, \
                     scale, stream
-    if (dtype == KVZ_F16) {
-        if (D == 128) return fprefill::launch<_Float16, 128>(KVZ_FP_ARGS);
-        return fprefill::launch<_Float16, 64>(KVZ_FP_ARGS);
-    }
-    if (D == 128) return fprefill::launch<__bf16, 128>(KVZ_FP_ARGS);
-    return fprefill::launch<__bf16, 64>(KVZ_FP_ARGS);
+#define KVZ_FP_CALL(T, DD) return fprefill::launch<T, DD>(KVZ_FP_ARGS)
+    KVZ_DISPATCH_HALF_D(dtype, D, KVZ_FP_CALL);
+#undef KVZ_FP_CALL
 #undef KVZ_FP_ARGS
 }

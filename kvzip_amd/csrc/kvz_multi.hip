@@ -22,7 +22,7 @@
 // nothing to keep in step with the caches.  A block finds its (segment, key range) with wave-uniform scalar work from those prefixes
 // (up to 127 compares against constant kernel-argument offsets): batches of scalar loads from the kernel-argument segment, independent of
 // each other.
-#include "kvz_common.h"
+#include "kvz_wave_tile.h"
 #include "../../include/kvzip_hip_multi.h"
 
 #include <limits.h>
@@ -30,42 +30,13 @@
 namespace kvz {
 namespace multi {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef short s4 __attribute__((ext_vector_type(4)));
-typedef short s8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Half;
-template <> struct Half<_Float16> {
-    typedef h8 v8;
-    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Half<__bf16> {
-    typedef b8 v8;
-    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
 constexpr int MK_THREADS = 512;
 constexpr int MK_WAVES = 8;
-constexpr int MK_KT = 32;            // keys per wave tile
-constexpr int MK_RT = 16;            // query rows per row tile (MFMA N)
 constexpr int MK_MAXB = 16;          // caches
 constexpr int MK_MAXH = 64;          // KV heads
 constexpr int MK_MAXS = 128;         // segments: B * Hkv
 constexpr int MK_MAXG = 64;          // query heads per KV head
 constexpr int MK_SCAN = 16;          // prefix entries compared per batch of scalar loads
-
-template <int D> struct Cfg {
-    static constexpr int ROW_BYTES = D * 2;
-    static constexpr int VSTRIDE = ROW_BYTES + 32;          // padded LDS row: conflict-free tr reads
-    static constexpr int WAVE_LDS = MK_KT * VSTRIDE;        // bytes of V staging per wave
-    static constexpr int KK = D / 32;
-    static constexpr int DB = D / 16;
-    static constexpr int CPR = ROW_BYTES / 16;
-    static constexpr int VLOADS = MK_KT * CPR / WAVE;
-};
 
 // the segment table, by value.  Segment s = b * Hkv + h.  Work items are numbered segment after segment: segment s owns items
 // item0[s] .. item0[s + 1] - 1 (none when cache b is inactive).
@@ -83,7 +54,7 @@ __global__ __launch_bounds__(MK_THREADS) void multi_attn_split_kernel(
     const T* __restrict__ q, Table tb, const T* __restrict__ k_new, const T* __restrict__ v_new, int64_t kn_bstride, int64_t kn_hstride,
     int64_t vn_bstride, int64_t vn_hstride, int S, int Hkv, int G, int chunk, float scale, float* __restrict__ part_o,
     float* __restrict__ part_ml, int n_rtiles) {
-    typedef Cfg<D> C;
+    typedef TileCfg<D> C;
     typedef typename Half<T>::v8 v8;
     // ---- this block's work item: (cache, head, key range) from the item prefixes (all wave-uniform scalar work) ----
     const int bx = blockIdx.x;             // (the grid has exactly as many blocks as there are items)
@@ -125,7 +96,7 @@ __global__ __launch_bounds__(MK_THREADS) void multi_attn_split_kernel(
     char* wl = lds + wave * C::WAVE_LDS;
 
     // ---- stationary Q fragment (B operand of S^T = K.Q^T): col = query row, k = head-dim slice ----
-    const int qrow = rt * MK_RT + l15;
+    const int qrow = rt * TILE_RT + l15;
     const bool qvalid = qrow < G;
     v8 qf[C::KK];
     {
@@ -142,7 +113,7 @@ __global__ __launch_bounds__(MK_THREADS) void multi_attn_split_kernel(
     f4 o[C::DB];
 #pragma unroll
     for (int i = 0; i < C::DB; ++i) o[i] = f4{0.f, 0.f, 0.f, 0.f};
-    const float sl2 = scale * 1.44269504088896340736f;  // work in the exp2 domain
+    const float sl2 = scale * LOG2E;  // work in the exp2 domain
 
     auto load_tile = [&](u32x4 (&kr)[2][C::KK], u32x4 (&vr)[C::VLOADS], int t0) {
 #pragma unroll
@@ -218,8 +189,8 @@ __global__ __launch_bounds__(MK_THREADS) void multi_attn_split_kernel(
     // The wave's tiles, one requested AHEAD of the one being computed; the steady-state loop issues the next tile's loads
     // UNCONDITIONALLY and the last tile is computed after the loop (the load structure of varlen_attn_split2_kernel: its comment
     // records what the conditional form cost).
-    const int t_first = c0 + wave * MK_KT;
-    constexpr int T_STEP = MK_WAVES * MK_KT;
+    const int t_first = c0 + wave * TILE_KT;
+    constexpr int T_STEP = MK_WAVES * TILE_KT;
     if (t_first < c1) {
         load_tile(kraw, vraw, t_first);
         int t0 = t_first;
@@ -241,10 +212,10 @@ __global__ __launch_bounds__(MK_THREADS) void multi_attn_split_kernel(
     l_run += __shfl_xor(l_run, 16, 64);
     l_run += __shfl_xor(l_run, 32, 64);
     constexpr int WSTR = D + 4;                          // floats per staged row
-    static_assert((MK_RT * WSTR + 2 * MK_RT) * 4 <= C::WAVE_LDS, "the wave's V tile holds its merge staging");
+    static_assert((TILE_RT * WSTR + 2 * TILE_RT) * 4 <= C::WAVE_LDS, "the wave's V tile holds its merge staging");
     float* wo = reinterpret_cast<float*>(wl);            // [16 q][D + 4]
-    float* wm = wo + MK_RT * WSTR;                       // [16] m, [16] l
-    const int rows_valid = min(MK_RT, G - rt * MK_RT);
+    float* wm = wo + TILE_RT * WSTR;                       // [16] m, [16] l
+    const int rows_valid = min(TILE_RT, G - rt * TILE_RT);
     if (l15 < rows_valid) {
 #pragma unroll
         for (int db = 0; db < C::DB; ++db) *reinterpret_cast<f4*>(wo + l15 * WSTR + db * 16 + quad * 4) = o[db];
@@ -252,13 +223,13 @@ __global__ __launch_bounds__(MK_THREADS) void multi_attn_split_kernel(
     }
     __syncthreads();
 
-    const int64_t pbase = ((int64_t)bx * n_rtiles + rt) * MK_RT;  // partial slot of this item
+    const int64_t pbase = ((int64_t)bx * n_rtiles + rt) * TILE_RT;  // partial slot of this item
     for (int e = threadIdx.x; e < rows_valid * (D / 4); e += MK_THREADS) {
         const int qq = e / (D / 4), d = (e % (D / 4)) * 4;
         float mw[MK_WAVES], M = -INFINITY;
 #pragma unroll
         for (int w = 0; w < MK_WAVES; ++w) {
-            mw[w] = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS)[MK_RT * WSTR + qq];
+            mw[w] = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS)[TILE_RT * WSTR + qq];
             M = fmaxf(M, mw[w]);
         }
         f4 acc4 = f4{0.f, 0.f, 0.f, 0.f};
@@ -269,7 +240,7 @@ __global__ __launch_bounds__(MK_THREADS) void multi_attn_split_kernel(
             const float wgt = (mw[w] == -INFINITY) ? 0.f : exp2f(mw[w] - M);
             const f4 ov = *reinterpret_cast<const f4*>(pw + qq * WSTR + d);
             acc4[0] += wgt * ov[0]; acc4[1] += wgt * ov[1]; acc4[2] += wgt * ov[2]; acc4[3] += wgt * ov[3];
-            lsum += wgt * pw[MK_RT * WSTR + 16 + qq];
+            lsum += wgt * pw[TILE_RT * WSTR + 16 + qq];
         }
         *reinterpret_cast<f4*>(part_o + (pbase + qq) * D + d) = acc4;
         if (d == 0) *reinterpret_cast<float2*>(part_ml + (pbase + qq) * 2) = make_float2(M, lsum);
@@ -293,8 +264,8 @@ __global__ __launch_bounds__(CB_THREADS) void multi_attn_combine_kernel(const fl
     }
     const int first_item = tb.item0[s];
     const int n = tb.item0[s + 1] - first_item;   // (>= 1: every segment of a live cache has an item)
-    const int64_t base = ((int64_t)first_item * n_rtiles + g / MK_RT) * MK_RT + g % MK_RT;
-    const int64_t istride = (int64_t)n_rtiles * MK_RT;
+    const int64_t base = ((int64_t)first_item * n_rtiles + g / TILE_RT) * TILE_RT + g % TILE_RT;
+    const int64_t istride = (int64_t)n_rtiles * TILE_RT;
 
     __shared__ float s_red[CB_THREADS / WAVE];
     __shared__ float s_acc[SLICES][D];
@@ -358,25 +329,16 @@ __global__ __launch_bounds__(CB_THREADS) void multi_attn_combine_kernel(const fl
     }
 }
 
-// work items a step is cut into: the decode kernel's rule with S segments in the place of Hkv heads (every segment rounds its item count
-// up, so a step has at most target + S items: one block per CU; kvz_attn.hip: attn_items)
-static inline int multi_items(int S) {
-    const int t = tunable(TUNE_ATTN_ITEMS);
-    if (t > 0) return t;
-    const int cus = device_cus();
-    return S < cus * 3 / 4 ? cus - S : cus / 4;
-}
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct MultiWs { float* part_ml; float* part_o; size_t items; size_t bytes; };
 static inline MultiWs multi_ws(void* ws, int B, int Hkv, int G, int D) {
-    const int S = B * Hkv, n_rtiles = (G + MK_RT - 1) / MK_RT;
+    const int S = B * Hkv, n_rtiles = (G + TILE_RT - 1) / TILE_RT;
     MultiWs w;
-    w.items = (size_t)multi_items(S) + S;
+    w.items = (size_t)target_items(S) + S;
     char* p = reinterpret_cast<char*>(ws);
     w.part_ml = reinterpret_cast<float*>(p);
-    p += align256(w.items * n_rtiles * MK_RT * 2 * sizeof(float));
+    p += align256(w.items * n_rtiles * TILE_RT * 2 * sizeof(float));
     w.part_o = reinterpret_cast<float*>(p);
-    p += align256(w.items * n_rtiles * MK_RT * D * sizeof(float));
+    p += align256(w.items * n_rtiles * TILE_RT * D * sizeof(float));
     w.bytes = (size_t)(p - reinterpret_cast<char*>(ws));
     return w;
 }
@@ -385,7 +347,7 @@ template <typename T, int D>
 static int launch_multi(const void* q, const Table& tb, int items, int chunk, const void* k_new, const void* v_new, int64_t kn_b,
                         int64_t kn_h, int64_t vn_b, int64_t vn_h, int B, int Hkv, int G, float scale, void* out, const MultiWs& w,
                         hipStream_t stream) {
-    const int n_rtiles = (G + MK_RT - 1) / MK_RT;
+    const int n_rtiles = (G + TILE_RT - 1) / TILE_RT;
     ProfScope ps("multi_attn", stream);
     if (items > 0) {  // (no live cache: nothing to attend, the combine writes the zeros)
         hipLaunchKernelGGL((multi_attn_split_kernel<T, D>), dim3(items, n_rtiles), dim3(MK_THREADS), 0, stream,
@@ -456,10 +418,8 @@ extern "C" int kvz_multi_attn_append(const void* q, void* const* k_ptrs_host, vo
     const MultiWs w = multi_ws(ws, B, Hkv, G, D);
     KVZ_REQUIRE(ws_bytes >= w.bytes, KVZ_EWORKSPACE, "kvz_multi_attn_append: workspace too small (%zu bytes, %zu needed)", ws_bytes, w.bytes);
     // the key ranges: chunks of the SUM of the live segment lengths, a multiple of 128 keys; every live segment at least one
-    const int target = multi_items(S);
-    int64_t chunk64 = (total + target - 1) / target;
-    chunk64 = (chunk64 + 127) / 128 * 128;
-    if (chunk64 < 128) chunk64 = 128;
+    const int target = target_items(S);
+    const int64_t chunk64 = chunk_of(total, target);
     KVZ_REQUIRE(chunk64 <= INT_MAX - 128, KVZ_EINVAL, "kvz_multi_attn_append: %lld keys in one step", (long long)total);
     const int chunk = (int)chunk64;
     int items = 0;
@@ -479,11 +439,8 @@ extern "C" int kvz_multi_attn_append(const void* q, void* const* k_ptrs_host, vo
                 w.items);
 #define KVZ_MULTI_ARGS q, tb, items, chunk, k_new, v_new, k_new_batch_stride, k_new_head_stride, v_new_batch_stride, v_new_head_stride, B, \
                        Hkv, G, scale, out, w, stream
-    if (dtype == KVZ_F16) {
-        if (D == 128) return launch_multi<_Float16, 128>(KVZ_MULTI_ARGS);
-        return launch_multi<_Float16, 64>(KVZ_MULTI_ARGS);
-    }
-    if (D == 128) return launch_multi<__bf16, 128>(KVZ_MULTI_ARGS);
-    return launch_multi<__bf16, 64>(KVZ_MULTI_ARGS);
+#define KVZ_MULTI_CALL(T, DD) return launch_multi<T, DD>(KVZ_MULTI_ARGS)
+    KVZ_DISPATCH_HALF_D(dtype, D, KVZ_MULTI_CALL);
+#undef KVZ_MULTI_CALL
 #undef KVZ_MULTI_ARGS
 }

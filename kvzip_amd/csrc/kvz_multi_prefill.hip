@@ -26,7 +26,7 @@
 // Tables: K,V base pointers and offsets per cache, cu_q, start, base length and FIRST WORK ITEM per segment travel BY VALUE as kernel
 // arguments (1928 bytes of table, 2.0 KB of the 4 KB there are with the other arguments).  A block finds its segment with wave-uniform
 // scalar work from the item prefixes (kvz_multi.hip's prefix count, up to 127 compares), then group and part by two divisions.
-#include "kvz_common.h"
+#include "kvz_wave_tile.h"
 #include "../../include/kvzip_hip_multi_prefill.h"
 
 #include <limits.h>
@@ -34,48 +34,14 @@
 namespace kvz {
 namespace mprefill {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-typedef short s4 __attribute__((ext_vector_type(4)));
-typedef short s8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Half;
-template <> struct Half<_Float16> {
-    typedef h8 v8;
-    typedef h4 v4;
-    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Half<__bf16> {
-    typedef b8 v8;
-    typedef b4 v4;
-    __device__ static inline f4 mfma(v8 a, v8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
 constexpr int MP_WAVES = 4;          // row tiles of one block (one wave each, one wave per SIMD)
 constexpr int MP_THREADS = MP_WAVES * WAVE;
-constexpr int MP_KT = 32;            // keys per tile
-constexpr int MP_RT = 16;            // query rows per row tile (MFMA N)
-constexpr int MP_GROUP = MP_WAVES * MP_RT;   // query rows of a work item = partial slots of an item
+constexpr int MP_GROUP = MP_WAVES * TILE_RT;   // query rows of a work item = partial slots of an item
 constexpr int MP_MAXB = 16;          // caches
 constexpr int MP_MAXH = 64;          // KV heads
 constexpr int MP_MAXS = 128;         // segments: B * Hkv
 constexpr int MP_MAXG = 64;          // query heads per KV head
 constexpr int MP_SCAN = 16;          // prefix entries compared per batch of scalar loads
-
-template <int D> struct Cfg {
-    static constexpr int ROW_BYTES = D * 2;
-    static constexpr int VSTRIDE = ROW_BYTES + 32;          // padded LDS row: conflict-free tr reads (kvz_multi.hip)
-    static constexpr int WAVE_LDS = MP_KT * VSTRIDE;        // bytes of V staging per wave
-    static constexpr int KK = D / 32;
-    static constexpr int DB = D / 16;
-    static constexpr int CPR = ROW_BYTES / 16;
-    static constexpr int VLOADS = MP_KT * CPR / WAVE;
-};
 
 // the tables, by value.  Segment s = b * Hkv + h.  Work items are numbered segment after segment, inside a segment group after group,
 // inside a group the key ranges and then the triangle: segment s owns items item0[s] .. item0[s + 1] - 1 (none when n_b = 0).
@@ -90,7 +56,7 @@ struct Table {
 };
 
 __device__ __host__ static inline int groups_of(int n_b, int G) {
-    return ((n_b * G + MP_RT - 1) / MP_RT + MP_WAVES - 1) / MP_WAVES;
+    return ((n_b * G + TILE_RT - 1) / TILE_RT + MP_WAVES - 1) / MP_WAVES;
 }
 
 template <typename T, int D>
@@ -98,7 +64,7 @@ __global__ __launch_bounds__(MP_THREADS) void multi_prefill_split_kernel(
     const T* __restrict__ q, int64_t qs_head, int64_t qs_group, int64_t qs_pos, Table tb, const T* __restrict__ k_new,
     const T* __restrict__ v_new, int64_t kn_h, int64_t kn_p, int64_t vn_h, int64_t vn_p, int S, int Hkv, int G, int chunk, float scale,
     float* __restrict__ part_o, float* __restrict__ part_ml) {
-    typedef Cfg<D> C;
+    typedef TileCfg<D> C;
     typedef typename Half<T>::v8 v8;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -124,7 +90,7 @@ __global__ __launch_bounds__(MP_THREADS) void multi_prefill_split_kernel(
     const int part = idx - grp * (kc + 1);
     const bool tri = part == kc;                            // the run's own new rows
     const int R = n_b * G;                                  // query rows of the run per KV head
-    const int ntiles = (R + MP_RT - 1) / MP_RT;
+    const int ntiles = (R + TILE_RT - 1) / TILE_RT;
     if (n_b <= 0) return;                                   // (never taken: a cache without positions owns no item)
 
     const int64_t seg = tb.start[s];
@@ -149,11 +115,11 @@ __global__ __launch_bounds__(MP_THREADS) void multi_prefill_split_kernel(
     // ---- this wave's row tile ----
     const int tile = grp * MP_WAVES + wave;
     if (tile >= ntiles) return;                             // (wave-uniform; the kernel has no barrier)
-    const int r_l = tile * MP_RT + l15;                     // this lane's query row (a column of S^T and O^T)
+    const int r_l = tile * TILE_RT + l15;                     // this lane's query row (a column of S^T and O^T)
     const bool rvalid = r_l < R;
     const int p_l = rvalid ? r_l / G : 0;
     const int g_l = r_l - p_l * G;
-    const int r_last = min(tile * MP_RT + MP_RT - 1, R - 1);
+    const int r_last = min(tile * TILE_RT + TILE_RT - 1, R - 1);
     // the keys the wave visits, [k0, kend) of its source, and the keys this lane's row sees of them (key < limit)
     const int k0 = tri ? 0 : part * chunk;
     const int kend = tri ? r_last / G + 1 : min(old, k0 + chunk);      // (> k0: a key range is never empty)
@@ -165,7 +131,7 @@ __global__ __launch_bounds__(MP_THREADS) void multi_prefill_split_kernel(
 
     __shared__ __attribute__((aligned(16))) char lds[MP_WAVES * C::WAVE_LDS];
     char* wl = lds + wave * C::WAVE_LDS;
-    const float sl2 = scale * 1.44269504088896340736f;      // work in the exp2 domain
+    const float sl2 = scale * LOG2E;      // work in the exp2 domain
 
     // stationary Q fragment (B operand of S^T = K.Q^T): col = query row, k = head-dim slice
     v8 qf[C::KK];
@@ -260,9 +226,9 @@ __global__ __launch_bounds__(MP_THREADS) void multi_prefill_split_kernel(
     load_k(kraw, k0);
     load_v(vraw, k0);
 #pragma unroll 1
-    for (int t0 = k0; t0 < kend; t0 += MP_KT) {
-        load_k(knext, t0 + MP_KT);
-        load_v(vnext, t0 + MP_KT);
+    for (int t0 = k0; t0 < kend; t0 += TILE_KT) {
+        load_k(knext, t0 + TILE_KT);
+        load_v(vnext, t0 + TILE_KT);
         compute_tile(kraw, vraw, t0);
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub)
@@ -277,7 +243,7 @@ __global__ __launch_bounds__(MP_THREADS) void multi_prefill_split_kernel(
     lr += __shfl_xor(lr, 16, 64);
     lr += __shfl_xor(lr, 32, 64);
     if (!rvalid) return;
-    const int64_t slot = (int64_t)bx * MP_GROUP + wave * MP_RT + l15;
+    const int64_t slot = (int64_t)bx * MP_GROUP + wave * TILE_RT + l15;
     float* po = part_o + slot * D + quad * 4;
 #pragma unroll
     for (int db = 0; db < C::DB; ++db) *reinterpret_cast<f4*>(po + db * 16) = o[db];
@@ -328,14 +294,6 @@ __global__ __launch_bounds__(CB_THREADS) void multi_prefill_combine_kernel(const
     }
 }
 
-// key-range items a call aims at: kvz_multi.hip's rule (one block per CU; attn_items overrides)
-static inline int target_items(int S) {
-    const int t = tunable(TUNE_ATTN_ITEMS);
-    if (t > 0) return t;
-    const int cus = device_cus();
-    return S < cus * 3 / 4 ? cus - S : cus / 4;
-}
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct Ws { float* part_ml; float* part_o; size_t items; size_t bytes; };
 static inline Ws workspace(void* ws, int T, int B, int Hkv, int G, int D) {
     const size_t rg = (size_t)Hkv * ((size_t)T * G / MP_GROUP + B);   // >= the (segment, group) pairs of any packing of T positions
@@ -437,9 +395,7 @@ extern "C" int kvz_multi_prefill(const void* q, int64_t q_stride_head, int64_t q
     KVZ_REQUIRE(ws_bytes >= w.bytes, KVZ_EWORKSPACE, "kvz_multi_prefill: workspace too small (%zu bytes, %zu needed)", ws_bytes, w.bytes);
     // the key ranges: chunks of the weighted sum of the old lengths, a multiple of 128 keys
     const int target = target_items(S);
-    int64_t chunk64 = (weighted + target - 1) / target;
-    chunk64 = (chunk64 + 127) / 128 * 128;
-    if (chunk64 < 128) chunk64 = 128;
+    const int64_t chunk64 = chunk_of(weighted, target);
     KVZ_REQUIRE(chunk64 <= INT_MAX - 128, KVZ_EINVAL, "kvz_multi_prefill: %lld keys in one call", (long long)weighted);
     const int chunk = (int)chunk64;
     int64_t items = 0;
@@ -458,11 +414,8 @@ extern "C" int kvz_multi_prefill(const void* q, int64_t q_stride_head, int64_t q
                 (long long)items, w.items);
 #define KVZ_MP_ARGS q, q_stride_head, q_stride_group, q_stride_pos, tb, (int)items, chunk, k_new, v_new, k_new_head_stride, \
                     k_new_pos_stride, v_new_head_stride, v_new_pos_stride, B, Hkv, G, Ttot, scale, out, w, stream
-    if (dtype == KVZ_F16) {
-        if (D == 128) return launch<_Float16, 128>(KVZ_MP_ARGS);
-        return launch<_Float16, 64>(KVZ_MP_ARGS);
-    }
-    if (D == 128) return launch<__bf16, 128>(KVZ_MP_ARGS);
-    return launch<__bf16, 64>(KVZ_MP_ARGS);
+#define KVZ_MP_CALL(T, DD) return launch<T, DD>(KVZ_MP_ARGS)
+    KVZ_DISPATCH_HALF_D(dtype, D, KVZ_MP_CALL);
+#undef KVZ_MP_CALL
 #undef KVZ_MP_ARGS
 }
