@@ -108,6 +108,11 @@ MULTI_PREFILL_SIGNATURES = {
                                _f, _i, _vp, _vp, _sz, _vp]),
 }
 
+# the entry point of include/kvzip_hip_branch.h (moving tail rows between the branch slots of a fork: beam search), bound by load()
+BRANCH_SIGNATURES = {
+    "kvz_fork_branch_copy": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -134,7 +139,8 @@ def load() -> C.CDLL:
         fn.restype = res
         fn.argtypes = args
     for header, table in (("kvzip_hip_tighten.h", EXT_SIGNATURES), ("kvzip_hip_multi.h", MULTI_SIGNATURES),
-                          ("kvzip_hip_prefill.h", PREFILL_SIGNATURES), ("kvzip_hip_multi_prefill.h", MULTI_PREFILL_SIGNATURES)):
+                          ("kvzip_hip_prefill.h", PREFILL_SIGNATURES), ("kvzip_hip_multi_prefill.h", MULTI_PREFILL_SIGNATURES),
+                          ("kvzip_hip_branch.h", BRANCH_SIGNATURES)):
         for name, (res, args) in table.items():
             fn = getattr(lib, name, None)
             if fn is None:   # (a library built before the header existed: same ABI version, so say what to do)

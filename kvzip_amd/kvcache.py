@@ -614,6 +614,38 @@ class DecodeGraph:
         return self.out
 
 
+def plan_branch_reorder(parents: Sequence[int], n_slots: int) -> Tuple[List[int], List[Tuple[int, int]]]:
+    """Where the hypotheses of a beam-search step live and what has to be copied for it (pure host logic, deterministic).
+    ``parents[i]`` is the branch slot whose state hypothesis i continues (at most ``n_slots`` hypotheses; a parent may appear several
+    times or not at all).  -> ``(slots, pairs)``: hypothesis i lives in ``slots[i]`` afterwards and ``pairs`` lists the
+    ``(src, dst)`` slot copies that make it so.  The first child of a parent stays in the parent's slot, with no copy; every further
+    child goes to a slot whose occupant has no child, lowest slot first.  A pure permutation of survivors therefore costs nothing, the
+    number of copies is the number of children beyond each parent's first (with all slots in use: the number of dropped hypotheses),
+    and sources (slots with a child) and destinations (slots without) are disjoint by construction - what the in-place copy of
+    ``kvz_fork_branch_copy`` needs."""
+    parents = [int(p) for p in parents]
+    n_slots = int(n_slots)
+    if len(parents) > n_slots:
+        raise ValueError(f"plan_branch_reorder: {len(parents)} hypotheses for {n_slots} slots")
+    for p in parents:
+        if not 0 <= p < n_slots:
+            raise ValueError(f"plan_branch_reorder: parent slot {p} outside [0, {n_slots})")
+    has_child = set(parents)
+    free = [s for s in range(n_slots) if s not in has_child]      # ascending: lowest slot first
+    slots: List[int] = []
+    pairs: List[Tuple[int, int]] = []
+    kept = set()
+    for p in parents:
+        if p not in kept:
+            kept.add(p)
+            slots.append(p)
+        else:
+            d = free.pop(0)                                        # (there is one: every hypothesis beyond a parent's first leaves a slot childless)
+            slots.append(d)
+            pairs.append((p, d))
+    return slots, pairs
+
+
 class ForkedCache:
     """``n_branches`` concurrent queries over ONE pruned slack-layout ``EvictCache`` (``EvictCache.fork``; no reference counterpart:
     batch is 1 there).  The branches share the base cache's flat K,V read-only - its rows, segment starts and lengths as they were at
@@ -627,10 +659,19 @@ class ForkedCache:
         SEVERAL branches back to back in one pass: one ``kvz_flash_fwd`` over the shared segments for all positions and one
         ``kvz_fork_prefill_tail`` for everything branch-private (append, causal attention inside each branch's tail, merge);
       * ``update_attend`` - ``[B, H, 1, D]`` queries, one new token per live branch.
-    The fork never changes ``info["offset"]``, ``_seen_tokens`` or any row of the base cache.  A prune or a slack growth of the base
-    moves the rows the fork points at: every hook then raises ``KvzError`` (as ``DecodeGraph.replay`` does)."""
+    The fork never changes ``info["offset"]``, ``_seen_tokens`` or any row of the base cache - until ``commit`` moves ONE branch's
+    rows into the base's slack and closes the fork.  A prune or a slack growth of the base moves the rows the fork points at: every
+    hook then raises ``KvzError`` (as ``DecodeGraph.replay`` does).
 
-    def __init__(self, base: "EvictCache", n_branches: int, tail_capacity: int = 256):
+    Beam search: ``reorder(parents)`` makes "hypothesis i continues from slot ``parents[i]``" true between two decode steps by copying
+    whole tails between slots (``kvz_fork_branch_copy``: survivors stay where they are, one copy per dropped hypothesis)."""
+
+    _closed = False   # commit() sets it on the instance: one branch's rows now belong to the base and every later hook raises
+
+    @staticmethod
+    def check_base(base, n_branches: int) -> None:
+        """Raise ``KvzError`` unless ``base`` can be forked into ``n_branches`` (what ``__init__`` asks; a caller that appends rows to
+        the base before it forks asks first, so that a refusal leaves the base as it was)."""
         if not (isinstance(base, EvictCache) and base.pruned and base.info.get("flatten") and base.layout == "slack"):
             raise ops.KvzError("fork: needs a pruned EvictCache in the slack layout")
         G = base.n_group_kv
@@ -639,6 +680,10 @@ class ForkedCache:
                                f"{ops.FORK_MAX_ROWS} query rows per KV head and {ops.FORK_MAX_BRANCHES} branches")
         if base.n_heads_kv > 64:
             raise ops.KvzError("fork: more than 64 KV heads")
+
+    def __init__(self, base: "EvictCache", n_branches: int, tail_capacity: int = 256):
+        self.check_base(base, n_branches)
+        G = base.n_group_kv
         offs = base.info["offset"]
         self.base, self.n_branches = base, int(n_branches)
         self.n_layers, self.n_heads_kv, self.n_group_kv = base.n_layers, base.n_heads_kv, G
@@ -697,6 +742,8 @@ class ForkedCache:
 
     def _check(self, layer_idx: int) -> None:
         base = self.base
+        if self._closed:
+            raise ops.KvzError("forked cache: the fork is closed (commit() moved a branch into the base cache): fork again")
         if self._epoch != base._layout_epoch or not base.info.get("flatten"):
             raise ops.KvzError("forked cache: the base cache was re-laid out since the fork (prune / slack growth): fork again")
         if base.info["offset"][layer_idx] < self._offset[layer_idx]:
@@ -718,6 +765,75 @@ class ForkedCache:
             self.tail_k[layer_idx], self.tail_v[layer_idx] = nk, nv
             self.tail_capacity = max(self.tail_capacity, cap)
         return self.tail_k[layer_idx], self.tail_v[layer_idx]
+
+    # -- beam search / keeping a branch ---------------------------------------------------------------------
+    def reorder(self, parents: Sequence[int]) -> List[int]:
+        """Continue hypothesis i from the state of branch slot ``parents[i]`` (a live slot; it may be named several times or not at
+        all): plan (``plan_branch_reorder``) and copy (``kvz_fork_branch_copy``: one launch for all layers) in one call.  -> ``slots``,
+        the slot hypothesis i lives in afterwards; the caller permutes its per-slot state (tokens, scores, positions) by it.  A
+        destination takes its source's tail rows and tail length in every layer and is live; slots left without a hypothesis are
+        retired.  Called between forward passes: a source's tail length must be the same in every layer."""
+        if self._packed is not None:
+            raise ops.KvzError("forked cache: reorder while a packing is selected (the packed first step has not run in every layer)")
+        for l in range(self.n_layers):
+            self._check(l)
+        parents = [int(p) for p in parents]
+        if len(parents) > self.n_branches:
+            raise ops.KvzError(f"forked cache: reorder got {len(parents)} hypotheses, the fork has {self.n_branches} slots")
+        for p in parents:
+            if not 0 <= p < self.n_branches:
+                raise ops.KvzError(f"forked cache: reorder: no branch {p} (the fork has {self.n_branches})")
+            if not self.active[p]:
+                raise ops.KvzError(f"forked cache: reorder: branch {p} is retired, nothing continues from it")
+        slots, pairs = plan_branch_reorder(parents, self.n_branches)
+        rows = []
+        for s, _ in pairs:
+            n = self.tail_len[0][s]
+            if any(self.tail_len[l][s] != n for l in range(self.n_layers)):
+                raise ops.KvzError(f"forked cache: reorder in the middle of a forward pass (the tail of branch {s} holds "
+                                   f"{[self.tail_len[l][s] for l in range(self.n_layers)]} rows per layer)")
+            rows.append(n)
+        if pairs and max(rows) > 0:
+            if any(t is None for t in self.tail_k):
+                raise ops.KvzError("forked cache: reorder: a layer's tails hold rows but were never allocated")
+            ops.fork_branch_copy(self.tail_k, self.tail_v, pairs, rows)
+        for (s, d), n in zip(pairs, rows):
+            for l in range(self.n_layers):
+                self.tail_len[l][d] = n
+        live = set(slots)
+        self.active = [b in live for b in range(self.n_branches)]
+        return slots
+
+    def commit(self, b: int) -> None:
+        """Keep branch ``b``: append its tail rows, all layers, to the BASE cache behind every head's current rows
+        (``kvz_append_inplace``, one call per layer, reading the tail through its own strides - no intermediate copy), growing the
+        base's slack first where needed.  Afterwards the base is exactly as after its own ``update`` of that many tokens
+        (``info["offset"]`` and ``_seen_tokens`` advanced by the branch's tail length) and the fork is closed: every later hook raises
+        ``KvzError``.  Nothing else of the base changes."""
+        if self._packed is not None:
+            raise ops.KvzError("forked cache: commit while a packing is selected")
+        b = int(b)
+        if not 0 <= b < self.n_branches:
+            raise ops.KvzError(f"forked cache: commit: no branch {b} (the fork has {self.n_branches})")
+        base = self.base
+        for l in range(self.n_layers):
+            self._check(l)
+            if base.info["offset"][l] != self._offset[l]:
+                raise ops.KvzError("forked cache: commit: rows were appended to the base cache since the fork (its slack behind the "
+                                   "rows the fork shares is not free): slice it back first")
+        t = self.tail_len[0][b]
+        if any(self.tail_len[l][b] != t for l in range(self.n_layers)):
+            raise ops.KvzError(f"forked cache: commit in the middle of a forward pass (the tail of branch {b} holds "
+                               f"{[self.tail_len[l][b] for l in range(self.n_layers)]} rows per layer)")
+        if t > 0:
+            if max(self._offset) + t > base.slack:
+                base._grow_slack(max(self._offset) + t)        # (the flat cache moves: this fork is closed below anyway)
+            for l in range(self.n_layers):
+                ops.append_inplace(base.key_cache[l], base.value_cache[l], self.tail_k[l][b:b + 1, :, :t], self.tail_v[l][b:b + 1, :, :t],
+                                   base.info["seg_start"][l], base.info["len_k"][l], self._offset[l])
+                base.info["offset"][l] = self._offset[l] + t
+            base._seen_tokens += t
+        self._closed = True
 
     # -- hooks ------------------------------------------------------------------------------------------
     def first_step(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,

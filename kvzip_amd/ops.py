@@ -633,6 +633,33 @@ def fork_prefill_tail(query: torch.Tensor, cu_q: Sequence[int], tail_k: torch.Te
     return out
 
 
+def fork_branch_copy(tail_k_list: Sequence[torch.Tensor], tail_v_list: Sequence[torch.Tensor], pairs: Sequence[Tuple[int, int]],
+                     rows: Sequence[int]) -> None:
+    """Move tail rows between the branch slots of a fork, all layers in one launch (``kvz_fork_branch_copy``,
+    include/kvzip_hip_branch.h).  tail_k_list / tail_v_list: per layer ``[B, Hkv, tail_cap, D]`` contiguous (the capacity may differ
+    between layers); for every layer, pair ``(src, dst) = pairs[i]`` and head: ``tail[dst, h, :rows[i]] = tail[src, h, :rows[i]]``,
+    K and V alike - the only bytes written.  Sources and destinations are disjoint sets and no destination appears twice (the library
+    refuses anything else: the copy is in place)."""
+    import ctypes as C
+    lib = _lib.load()
+    L, P = len(tail_k_list), len(pairs)
+    assert L >= 1 and len(tail_v_list) == L and len(rows) == P
+    B, Hkv, _, D = tail_k_list[0].shape
+    for k, v in zip(tail_k_list, tail_v_list):
+        assert k.shape == v.shape and k.shape[0] == B and k.shape[1] == Hkv and k.shape[3] == D and k.dtype == tail_k_list[0].dtype
+        assert k.is_contiguous() and v.is_contiguous() and v.dtype == k.dtype
+    _same_device(*tail_k_list, *tail_v_list)
+    kp = (C.c_void_p * L)(*[k.data_ptr() for k in tail_k_list])
+    vp = (C.c_void_p * L)(*[v.data_ptr() for v in tail_v_list])
+    cap = (C.c_int32 * L)(*[k.shape[2] for k in tail_k_list])
+    n = max(P, 1)
+    src = (C.c_int32 * n)(*[int(s) for s, _ in pairs])
+    dst = (C.c_int32 * n)(*[int(d) for _, d in pairs])
+    rw = (C.c_int32 * n)(*[int(r) for r in rows])
+    rc = lib.kvz_fork_branch_copy(kp, vp, cap, L, B, Hkv, D, tail_k_list[0].element_size(), src, dst, rw, P, _stream(tail_k_list[0]))
+    check(rc, "kvz_fork_branch_copy")
+
+
 # --------------------------------------------------------------------------------------------------
 # batched decode: one token for several INDEPENDENT pruned caches (include/kvzip_hip_multi.h; no reference counterpart)
 # --------------------------------------------------------------------------------------------------

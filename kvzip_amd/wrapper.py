@@ -23,7 +23,7 @@ from typing import List, Optional, Tuple, Union
 
 import torch
 
-from .kvcache import CacheBatch, EvictCache, RetainCache
+from .kvcache import CacheBatch, EvictCache, ForkedCache, RetainCache
 from .monkeypatch import replace_attn
 from .ops import KvzError
 from .template import template
@@ -127,6 +127,7 @@ class ModelKVzip:
         self.fork_packed_first = True
         self.multi_packed_first = True   # generate_multi: the first steps of a wave as ONE packed forward pass (CacheBatch.first_step)
         self.multi_max_caches = 16   # caches of one batched decode wave (generate_multi), besides the kernel's own limit of 128 // Hkv
+        self.last_beam_hypotheses: List[Tuple[float, List[int]]] = []   # generate_beam: (score, generated tokens) of its hypotheses
         self.sample_generator: Optional[torch.Generator] = None   # seed source of do_sample=True (None: torch's global generator)
         self.sys_prompt_ids = torch.zeros((1, 0), dtype=torch.long, device=self.device)
         self.postfix_ids = torch.zeros((1, 0), dtype=torch.long, device=self.device)
@@ -320,21 +321,30 @@ class ModelKVzip:
 
     @_on_model_device
     @torch.inference_mode()
-    def generate_batch(self, queries, kv, return_ids: bool = False) -> list:
+    def generate_batch(self, queries, kv, return_ids: bool = False, keep: Optional[int] = None) -> list:
         """Responses to several queries over ONE pruned cache, decoded together (no reference counterpart: the reference answers the
         queries of a context one after the other, eval.py).  Every query becomes a branch of ``kv.fork(...)``: the first steps (the
         query tokens) of all branches of a wave run as ONE packed forward pass (``fork_packed_first``, the default; ``False``: one
         forward per branch at batch 1), then all live branches decode in one batch whose attention reads the shared context once per
         step.  Same knobs as ``generate`` (``gen_kwargs``; the last token of every answer is dropped as there); a branch stops at EOS
         or ``max_new_tokens`` while the others go on.  More queries than one launch takes (``64 // G`` branches, at most 16) run in
-        waves.  ``kv`` is left exactly as it was: nothing is appended to it, so there is nothing to slice; ``update_cache=True`` is
-        not offered.  Answers agree with ``generate`` up to the summation order of the attention (an argmax may tie)."""
+        waves.  ``kv`` is left exactly as it was: nothing is appended to it, so there is nothing to slice.  ``keep=i`` is this path's
+        ``update_cache=True``: the cache afterwards holds query i and its answer as after ``generate(queries[i], kv,
+        update_cache=True)`` - branch i's rows are appended to the base (``ForkedCache.commit``) and ``prefill_ids`` grows - so that a
+        multi-turn conversation goes on from the kept branch; only offered when all queries fit one wave (``KvzError`` otherwise).
+        Answers agree with ``generate`` up to the summation order of the attention (an argmax may tie)."""
         ids = [self.encode(q) if isinstance(q, str) else q.to(self.device) for q in queries]
         G = self.config.num_attention_heads // self.config.num_key_value_heads
         wave = max(1, min(self.fork_max_branches, 64 // G))
+        if keep is not None:
+            if not 0 <= int(keep) < len(ids):
+                raise KvzError(f"generate_batch: keep={keep} names none of the {len(ids)} queries")
+            if len(ids) > wave:
+                raise KvzError(f"generate_batch: keep= is offered when all queries fit one wave ({wave} branches here: 64 // G, at most "
+                               f"{self.fork_max_branches}); got {len(ids)} queries")
         answers: list = []
         for w0 in range(0, len(ids), wave):
-            answers += self._generate_wave(ids[w0:w0 + wave], kv)
+            answers += self._generate_wave(ids[w0:w0 + wave], kv, keep=keep)
         return answers if return_ids else [self.decode(a) for a in answers]
 
     def _packs_first_steps(self, lengths: List[int]) -> bool:
@@ -344,7 +354,7 @@ class ModelKVzip:
         goes to the per-branch loop, which fails on it as it always did.)"""
         return bool(self.fork_packed_first) and all(n > 0 for n in lengths)
 
-    def _generate_wave(self, ids: List[torch.Tensor], kv) -> List[torch.Tensor]:
+    def _generate_wave(self, ids: List[torch.Tensor], kv, keep: Optional[int] = None) -> List[torch.Tensor]:
         B = len(ids)
         max_new = self.gen_kwargs["max_new_tokens"]
         fork = kv.fork(B, tail_capacity=max(x.shape[1] for x in ids) + max_new)
@@ -387,7 +397,162 @@ class ModelKVzip:
             for b in range(B):
                 if live[b]:
                     take(b, self.next_token(logits[b:b + 1], self.gen_kwargs, self.sample_generator))
-        return [torch.cat(o, dim=1)[:, :-1] for o in out_ids]
+        answers = [torch.cat(o, dim=1)[:, :-1] for o in out_ids]
+        if keep is not None:   # the kept branch's tail - its query rows and the rows of its answer - becomes part of the base cache
+            fork.commit(keep)
+            if kv.prefill_ids is not None:
+                kv.prefill_ids = torch.cat([kv.prefill_ids, ids[keep], answers[keep]], dim=1)
+        return answers
+
+    def _fork_limit(self, who: str, n: int) -> None:
+        G = self.config.num_attention_heads // self.config.num_key_value_heads
+        if n < 1 or n > 16 or n * G > 64:
+            raise KvzError(f"{who}: {n} branches x {G} query heads per KV head: one forked decode launch takes at most 64 query rows per "
+                           f"KV head (branches x G) and at most 16 branches")
+
+    @_on_model_device
+    @torch.inference_mode()
+    def generate_beam(self, query: Union[str, torch.Tensor], kv, num_beams: int = 4, length_penalty: float = 1.0,
+                      update_cache: bool = False, return_ids: bool = False, num_return: int = 1):
+        """Beam search over ONE pruned cache (no reference counterpart: the reference hands ``num_beams`` to HF ``generate``, which
+        replicates the whole cache per beam).  The query's first step runs ONCE on the base cache on the sequential path, as
+        ``generate``'s does; then the beams are the branches of ``kv.fork(num_beams)``, which sees the query rows as shared, so a
+        tail holds generated tokens only and a step reads the context once for all beams.  Per step: fp32 ``log_softmax`` of every live
+        beam's logits, the top ``2 * num_beams`` of the ``beams x V`` continuations by summed log-probability, walked best first - a
+        continuation that ends in EOS becomes a finished hypothesis if it ranks among the first ``num_beams``, the first ``num_beams``
+        others are the next beams - then ``fork.reorder(parents)`` moves the tails (one copy per dropped beam).  A hypothesis scores
+        ``sum_logprob / len ** length_penalty``, ``len`` counting every generated token, the last one included.  The search stops when
+        ``num_beams`` hypotheses are finished and no live beam can still beat the worst of them (for ``length_penalty > 0`` the bound
+        of a live beam is its sum over ``max_new_tokens ** length_penalty``), or at ``max_new_tokens``, where the live beams finish;
+        at most ``num_beams`` hypotheses are kept, the best ones.  ONE beam is greedy decoding and ends where ``generate`` ends: at the
+        first EOS (the rule above would let the runner-up token live on past it), whatever ``length_penalty`` says.
+        Returns the best hypothesis (``num_return > 1``: the list of the best ``num_return``), the last token dropped as ``generate``
+        drops it.  ``update_cache=False``: the cache is sliced back.  ``update_cache=True``: the cache keeps the query and the best
+        answer and ``prefill_ids`` grows as in ``generate`` - a hypothesis that was live at ``max_new_tokens`` has its rows in its
+        parent's tail and is committed from there (``ForkedCache.commit``); one that ended in EOS earlier may have lost its slot to
+        another beam, so its answer tokens run through the base cache in one sequential forward pass instead.  Sampling knobs are not
+        used; ``num_beams=1`` gives ``generate``'s greedy tokens.  ``last_beam_hypotheses`` keeps ``(score, tokens)`` of the kept
+        hypotheses of the last search, best first, every generated token included: the answers drop their last token, so the return
+        value cannot say what a score was taken over.  A cache that cannot be forked is refused before a row is appended to it."""
+        self._fork_limit("generate_beam", int(num_beams))
+        B = int(num_beams)
+        if not 1 <= int(num_return) <= B:
+            raise ValueError(f"generate_beam: num_return={num_return} outside [1, num_beams={B}]")
+        ForkedCache.check_base(kv, B)           # (the query's rows go to the base BEFORE the fork: ask now what fork() will ask)
+        seen_prev = kv._seen_tokens
+        input_ids = self.encode(query) if isinstance(query, str) else query.to(self.device)
+        max_new = self.gen_kwargs["max_new_tokens"]
+        eos = set(self.eos_token_ids)
+        lp = float(length_penalty)
+        logp = torch.log_softmax(self.model(input_ids, past_key_values=kv, use_cache=True).logits[:, -1].float(), dim=-1)
+        V = logp.shape[-1]
+        pos0 = kv.get_seq_length()              # position of the first generated token
+        fork = None
+        live = [(0, [], 0.0)]                   # (row of logp = branch slot, generated tokens, summed log-probability)
+        finished = []                           # (score, tokens, slot whose tail holds the rows of tokens[:-1] or None)
+        n_gen = 0
+        while live:
+            rows = torch.tensor([h[0] for h in live], device=self.device)
+            sums = torch.tensor([h[2] for h in live], dtype=torch.float32, device=self.device)
+            cand = (logp[rows] + sums[:, None]).view(-1)
+            top = torch.topk(cand, min(2 * B, cand.numel()))
+            n_gen += 1
+            nxt = []
+            for rank, (val, idx) in enumerate(zip(top.values.tolist(), top.indices.tolist())):
+                h, tok = live[idx // V], idx % V
+                if tok in eos:
+                    if rank < B:
+                        finished.append((val / n_gen ** lp, h[1] + [tok], None))
+                    continue
+                nxt.append((h[0], h[1] + [tok], val))
+                if len(nxt) == B:
+                    break
+            if B == 1 and finished:             # one beam: the greedy token is EOS, generate() stops here
+                break
+            if n_gen >= max_new:                # the token budget: the live beams finish, their rows still in their parents' tails
+                finished += [(val / n_gen ** lp, toks, slot if fork is not None else None) for slot, toks, val in nxt]
+                break
+            finished = sorted(finished, key=lambda f: -f[0])[:B]
+            if not nxt:
+                break
+            if len(finished) >= B:
+                best_live = max(val for _, _, val in nxt)
+                bound = best_live / (max_new if lp > 0 else n_gen) ** lp
+                if bound <= finished[-1][0]:
+                    break
+            if fork is None:
+                fork = kv.fork(B, tail_capacity=max(max_new, 1))
+            slots = fork.reorder([p for p, _, _ in nxt])
+            live = [(s, toks, val) for s, (_, toks, val) in zip(slots, nxt)]
+            cur = torch.zeros((B, 1), dtype=torch.long, device=self.device)
+            for s, toks, _ in live:
+                cur[s] = toks[-1]
+            pos = torch.full((B, 1), pos0 + n_gen - 1, dtype=torch.long, device=self.device)
+            logp = torch.log_softmax(self.model(cur, past_key_values=fork, use_cache=True, position_ids=pos).logits[:, -1].float(), dim=-1)
+        finished = sorted(finished, key=lambda f: -f[0])[:B]
+        best = finished[0]
+        self.last_beam_hypotheses = [(score, toks) for score, toks, _ in finished]   # best first; every token, the dropped last one included
+        answers = [torch.tensor([toks[:-1]], dtype=torch.long, device=self.device).view(1, -1) for _, toks, _ in finished[:int(num_return)]]
+        if not update_cache:
+            kv.slice(seen_prev)
+        else:
+            if best[2] is not None:
+                fork.commit(best[2])
+            elif answers[0].shape[1]:
+                self.model.model(answers[0], past_key_values=kv, use_cache=True)
+            if kv.prefill_ids is not None:
+                kv.prefill_ids = torch.cat([kv.prefill_ids, input_ids, answers[0]], dim=1)
+        out = answers if return_ids else [self.decode(a) for a in answers]
+        return out[0] if int(num_return) == 1 else out
+
+    @_on_model_device
+    @torch.inference_mode()
+    def generate_samples(self, query: Union[str, torch.Tensor], kv, n: int, return_ids: bool = False) -> list:
+        """``n`` answers to ONE query over one pruned cache (self-consistency, best-of-n; no reference counterpart).  The query's first
+        step runs once on the base cache, on the sequential path; the answers are the branches of ``kv.fork(n)``, which sees the
+        query rows as shared: every branch draws its own first token from the same logits (``gen_kwargs``: with ``do_sample=False``
+        all answers are ``generate``'s) and the branches decode together as in ``generate_batch``, the tails holding generated tokens
+        only.  More answers than one launch takes (``64 // G`` branches, at most 16) run in waves over the same query rows.  ``kv`` is
+        sliced back afterwards: it is left as it was; one that cannot be forked is refused before a row is appended to it."""
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"generate_samples: n={n}")
+        seen_prev = kv._seen_tokens
+        input_ids = self.encode(query) if isinstance(query, str) else query.to(self.device)
+        G = self.config.num_attention_heads // self.config.num_key_value_heads
+        wave = max(1, min(self.fork_max_branches, 16, 64 // G))
+        ForkedCache.check_base(kv, min(wave, n))   # (the query's rows go to the base BEFORE the fork: ask now what fork() will ask)
+        max_new = self.gen_kwargs["max_new_tokens"]
+        eos = self.eos_token_ids
+        first = self.model(input_ids, past_key_values=kv, use_cache=True).logits[:, -1]
+        pos0 = kv.get_seq_length()
+        answers: list = []
+        for w0 in range(0, n, wave):
+            B = min(wave, n - w0)
+            fork = kv.fork(B, tail_capacity=max(max_new, 1))
+            out_ids: List[List[torch.Tensor]] = [[] for _ in range(B)]
+            cur = torch.zeros((B, 1), dtype=torch.long, device=self.device)
+            pos = torch.full((B, 1), pos0, dtype=torch.long, device=self.device)
+            live = [True] * B
+
+            def take(b, nxt):
+                out_ids[b].append(nxt)
+                cur[b] = nxt[0]
+                if (eos and int(nxt) in eos) or len(out_ids[b]) >= max_new:
+                    live[b] = False
+                    fork.retire(b)
+
+            for b in range(B):
+                take(b, self.next_token(first, self.gen_kwargs, self.sample_generator))
+            while any(live):
+                logits = self.model(cur, past_key_values=fork, use_cache=True, position_ids=pos).logits[:, -1]
+                pos += 1
+                for b in range(B):
+                    if live[b]:
+                        take(b, self.next_token(logits[b:b + 1], self.gen_kwargs, self.sample_generator))
+            answers += [torch.cat(o, dim=1)[:, :-1] for o in out_ids]
+        kv.slice(seen_prev)
+        return answers if return_ids else [self.decode(a) for a in answers]
 
     @_on_model_device
     @torch.inference_mode()
