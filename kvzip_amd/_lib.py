@@ -113,6 +113,13 @@ BRANCH_SIGNATURES = {
     "kvz_fork_branch_copy": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
 }
 
+# the entry points of include/kvzip_hip_spec.h (one verify step of draft-and-verify decoding on a pruned cache), bound by load()
+SPEC_SIGNATURES = {
+    "kvz_spec_attn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "kvz_spec_attn_append": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _f, _i, _vp, _vp,
+                                  _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -140,7 +147,7 @@ def load() -> C.CDLL:
         fn.argtypes = args
     for header, table in (("kvzip_hip_tighten.h", EXT_SIGNATURES), ("kvzip_hip_multi.h", MULTI_SIGNATURES),
                           ("kvzip_hip_prefill.h", PREFILL_SIGNATURES), ("kvzip_hip_multi_prefill.h", MULTI_PREFILL_SIGNATURES),
-                          ("kvzip_hip_branch.h", BRANCH_SIGNATURES)):
+                          ("kvzip_hip_branch.h", BRANCH_SIGNATURES), ("kvzip_hip_spec.h", SPEC_SIGNATURES)):
         for name, (res, args) in table.items():
             fn = getattr(lib, name, None)
             if fn is None:   # (a library built before the header existed: same ABI version, so say what to do)

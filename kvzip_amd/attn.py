@@ -8,6 +8,7 @@ interface registry).  Hooks on the cache object, in this order (attention/attn.p
     update_attend()     the three of them in one launch                (generation step on a pruned slack-layout cache)
     first_step() / update_attend() of a ForkedCache                    (several queries decoding over one shared pruned cache)
     first_step() / update_attend() of a CacheBatch                     (several independent pruned caches decoding together)
+    verify_attend()     the three of them for t drafted positions      (inside `with kv.verifying():`, speculative decoding)
 
 The dense (pre-prune) attention — flash-attn's dense kernel in the reference (attention/attn.py:75-89) — runs on the
 library's multi-row kernel (``ops.flash_fwd`` -> ``kvz_flash_fwd``), registered as the attention implementation
@@ -97,6 +98,15 @@ def llama_qwen_attn_forward(self, hidden_states: torch.Tensor,
     if (q_len == 1 and getattr(kv, "pruned", None) and not getattr(kv, "get_score", None)
             and getattr(kv, "layout", None) == "slack" and hasattr(kv, "update_attend")):
         attn = kv.update_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling)
+        n_kv = self.config.num_key_value_heads
+        attn_output = attn.view(bsz, n_kv, q_len, -1, self.head_dim).transpose(1, 2).reshape(bsz, q_len, -1).contiguous()
+        return self.o_proj(attn_output), None
+    # verify step of speculative decoding (only inside `with kv.verifying():`): update + prepare + attend for the t drafted positions
+    # in one call that reads the kept rows once
+    if (q_len > 1 and bsz == 1 and getattr(kv, "_verifying", False) and getattr(kv, "pruned", None)
+            and not getattr(kv, "get_score", None) and getattr(kv, "layout", None) == "slack"
+            and q_len * (query_states.shape[1] // key_states.shape[1]) <= 64):
+        attn = kv.verify_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling)  # [Hkv*q_len, G, D]
         n_kv = self.config.num_key_value_heads
         attn_output = attn.view(bsz, n_kv, q_len, -1, self.head_dim).transpose(1, 2).reshape(bsz, q_len, -1).contiguous()
         return self.o_proj(attn_output), None

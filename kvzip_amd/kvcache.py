@@ -15,6 +15,7 @@ MI355X-first storage (sized for 288 GB of HBM3E):
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -537,6 +538,69 @@ class EvictCache(_CacheBase):
                                      offset_dev=self._dyn_off, out=out)
         self.info["offset"][layer_idx] = off + 1
         return out
+
+    # ---- speculative decoding: verify t drafted positions in one step, take the rejected ones back ------------------------------
+    @contextlib.contextmanager
+    def verifying(self):
+        """While inside, a forward pass of 2 .. 64 // G tokens on this pruned slack-layout cache takes ``verify_attend``
+        (kvzip_amd.attn).  Only the speculative loop sets it: without it every forward goes where it always went."""
+        prev, self._verifying = getattr(self, "_verifying", False), True
+        try:
+            yield self
+        finally:
+            self._verifying = prev
+
+    def verify_attend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
+                      softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Verify step (t consecutive new positions) on the pruned cache, slack layout: ``update`` + ``prepare`` + ``attend`` for
+        ``q_len = t`` in one call of ``kvz_spec_attn_append``, which reads the kept rows once (twice beyond 32 query rows per KV
+        head) and writes the t K,V rows into the slack of every head.  query ``[1, H, t, D]``, key / value ``[1, Hkv, t, D]``;
+        returns ``[Hkv*t, G, D]`` like ``attend``.  The cache bookkeeping (``_seen_tokens``, ``info["offset"]``) ends up exactly as
+        after the three separate calls; ``rewind`` takes positions back."""
+        assert self.info["flatten"] and self.layout == "slack" and query_states.shape[0] == 1
+        t, dim = query_states.shape[-2], query_states.shape[-1]
+        Hkv, G = self.n_heads_kv, self.n_group_kv
+        if layer_idx == 0:
+            self._seen_tokens += t
+        off = self.info["offset"][layer_idx]
+        if off + t > self.slack:
+            self._grow_slack(off + t)
+        q = query_states.reshape(Hkv, G, t, dim).transpose(1, 2).contiguous()                   # [Hkv, t, G, D]: row = p*G + g
+        ws = self._spec_workspace(t, dim, query_states.device)
+        if out is not None:
+            out = out.view(Hkv, t, G, dim)
+        out = ops.spec_attn_append(q, self.key_cache[layer_idx], self.value_cache[layer_idx], self.info["seg_start"][layer_idx],
+                                   self.info["len_k"][layer_idx], off, self.slack, key_states[0], value_states[0],
+                                   softmax_scale=softmax_scale, workspace=ws, meta_host=self._meta_host(layer_idx), out=out)
+        self.info["offset"][layer_idx] = off + t
+        return out.view(Hkv * t, G, dim)
+
+    def _spec_workspace(self, t: int, dim: int, device) -> torch.Tensor:
+        """Scratch of the verify step, one per number of 16-row tiles (its size depends on nothing else that changes between steps)."""
+        cache = getattr(self, "_spec_ws_cache", None)
+        if cache is None:
+            cache = self._spec_ws_cache = {}
+        key = ((t * self.n_group_kv + 15) // 16, dim)
+        need = int(ops._lib.load().kvz_spec_attn_workspace_bytes(t, self.n_heads_kv, self.n_group_kv, dim))
+        ws = cache.get(key)
+        if ws is None or ws.numel() < need or ws.device != torch.device(device):
+            ws = cache[key] = ops.spec_attn_workspace(t, self.n_heads_kv, self.n_group_kv, dim, device)
+        return ws
+
+    def rewind(self, n: int) -> None:
+        """Take back the last ``n`` appended positions (the rejected tail of a verify step): a host-side decrement of every layer's
+        offset and of ``_seen_tokens``, no launch.  The rows stay in the slack as garbage, exactly as after ``slice``, and the next
+        appended token overwrites them.  Slack layout only; ``n`` may not exceed what was appended since the prune or the last
+        ``slice``."""
+        n = int(n)
+        if not (self.info.get("flatten") and self.layout == "slack"):
+            raise ops.KvzError("rewind: only a pruned slack-layout cache takes appended positions back on the host (a dense or "
+                               "packed-layout cache: slice())")
+        have = min(self.info["offset"])
+        if n < 0 or n > have:
+            raise ops.KvzError(f"rewind: {n} positions, but {have} were appended since the prune or the last slice")
+        self.info["offset"] = [o - n for o in self.info["offset"]]
+        self._seen_tokens -= n
 
     def fork(self, n_branches: int, tail_capacity: int = 256) -> "ForkedCache":
         """``n_branches`` concurrent queries over this pruned cache: the branches share its rows read-only and each owns a private

@@ -581,6 +581,47 @@ def attn_merge_lse(o1: torch.Tensor, lse1: torch.Tensor, o2: torch.Tensor, lse2:
     return out
 
 
+# --------------------------------------------------------------------------------------------------
+# speculative decoding: one verify step of t consecutive positions on a pruned cache (no reference counterpart)
+# --------------------------------------------------------------------------------------------------
+SPEC_MAX_ROWS = 64      # query rows (positions x query heads per KV head) of one verify launch
+
+
+def spec_attn_workspace(t: int, Hkv: int, G: int, D: int, device) -> torch.Tensor:
+    """Scratch of ``spec_attn_append`` (partials of the key ranges and of the triangle); no initialisation needed."""
+    need = _lib.load().kvz_spec_attn_workspace_bytes(t, Hkv, G, D)
+    return torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+
+
+def spec_attn_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_start: Optional[torch.Tensor],
+                     k_len: Optional[torch.Tensor], k_len_offset: int, slack: int, k_new: torch.Tensor, v_new: torch.Tensor,
+                     softmax_scale: Optional[float] = None, workspace: Optional[torch.Tensor] = None, meta_host=None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One verify step on a pruned slack-layout cache (``kvz_spec_attn_append``).  q ``[Hkv, t, G, D]``; k_cache / v_cache
+    ``[rows, D]``, head h holding ``k_len[h] + k_len_offset`` rows from ``k_start[h]`` on (device arrays and / or ``meta_host``) with
+    ``slack`` free rows laid out behind every segment; k_new / v_new ``[Hkv, t, D]`` (any head / position stride).  Appends the t rows
+    behind every segment and returns ``[Hkv, t, G, D]``: position p attends to the old rows and to the new rows 0 .. p."""
+    lib = _lib.load()
+    Hkv, t, G, D = q.shape
+    assert q.is_contiguous() and k_cache.is_contiguous() and v_cache.is_contiguous()
+    assert k_new.shape == (Hkv, t, D) and v_new.shape == (Hkv, t, D) and k_new.stride(-1) == 1 and v_new.stride(-1) == 1
+    assert (k_start is None) == (k_len is None) and (k_start is not None or meta_host is not None)
+    assert k_start is None or (k_start.dtype == torch.int32 and k_len.dtype == torch.int32)
+    _same_device(q, k_cache, v_cache, k_new, v_new, workspace, out)
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty_like(q)
+    assert out.shape == q.shape and out.is_contiguous() and out.dtype == q.dtype
+    if workspace is None:
+        workspace = spec_attn_workspace(t, Hkv, G, D, q.device)
+    rc = lib.kvz_spec_attn_append(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(k_start), _ptr(k_len), int(k_len_offset),
+                                  meta_host, int(slack), k_new.data_ptr(), v_new.data_ptr(), k_new.stride(0), k_new.stride(1),
+                                  v_new.stride(0), v_new.stride(1), t, Hkv, G, D, float(scale), _dtype_code(q.dtype), out.data_ptr(),
+                                  workspace.data_ptr(), workspace.numel(), _stream(q))
+    check(rc, "kvz_spec_attn_append")
+    return out
+
+
 def fork_prefill_tail(query: torch.Tensor, cu_q: Sequence[int], tail_k: torch.Tensor, tail_v: torch.Tensor, tail_len: Sequence[int],
                       k_new: torch.Tensor, v_new: torch.Tensor, o_shared: torch.Tensor, lse_shared: torch.Tensor,
                       softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None,

@@ -319,6 +319,85 @@ class ModelKVzip:
             kv.prefill_ids = torch.cat([kv.prefill_ids, input_ids, a_ids], dim=1)
         return a_ids if return_ids else self.decode(a_ids)
 
+    def _draft_len(self, num_draft: Optional[int] = None) -> int:
+        """Drafted tokens per verify step (the step runs t = 1 + draft positions).  The default keeps t*G <= 32 query rows per KV
+        head - one block per work item, where the forked decode's step time holds - and a request is capped at t*G <= 64,
+        the kernel's limit.  Both come from the forked-decode table, not from a measurement of the verify kernel: a shape that
+        tools/spec_decode_bench.py flags as slower than the existing path gets its rule HERE."""
+        G = self.config.num_attention_heads // self.config.num_key_value_heads
+        cap = max(0, 64 // G - 1)
+        if num_draft is None:
+            return max(0, 32 // G - 1)
+        return max(0, min(int(num_draft), cap))
+
+    @_on_model_device
+    @torch.inference_mode()
+    def generate_speculative(self, query: Union[str, torch.Tensor], kv, draft=None, num_draft: Optional[int] = None,
+                             update_cache: bool = False, return_ids: bool = False, return_stats: bool = False):
+        """``generate`` by draft-and-verify on a pruned slack-layout cache, greedy (no reference counterpart).  After the query's
+        first step every further step asks the drafter for up to ``num_draft`` ids (``draft(history_ids, n)`` if given, else prompt
+        lookup over ``kv.prefill_ids ++ query ++ answer``, ``draft.lookup_draft``), runs ``[last token] ++ draft`` through the model
+        in ONE forward pass whose attention reads the kept rows once (``EvictCache.verify_attend``), keeps the longest prefix of the
+        draft the model agrees with plus the model's own token behind it, and takes the rejected positions back (``kv.rewind``).  An
+        empty draft is a plain decode step.  Same tokens as ``generate`` up to the summation order of the attention (an argmax may
+        tie); the answer ends at the first EOS or at ``max_new_tokens``, its last token is dropped and the cache is left as
+        ``generate`` leaves it.  ``return_stats``: also ``{"steps", "tokens", "drafted", "accepted"}`` (forward passes after the query's,
+        tokens they produced, ids drafted, ids accepted).  End-to-end gain depends on the drafter's hit rate."""
+        from .draft import accept_greedy, lookup_draft
+        if self.gen_kwargs.get("do_sample", False):
+            raise ValueError("generate_speculative is greedy: do_sample=True needs a distribution-preserving acceptance rule, use generate")
+        if not (isinstance(kv, EvictCache) and kv.pruned and kv.info.get("flatten") and kv.layout == "slack"):
+            raise ValueError("generate_speculative needs a pruned slack-layout EvictCache (the verify step appends to and rewinds the "
+                             "slack behind the kept rows): use generate for a dense or packed-layout cache")
+        seen_token_prev = kv._seen_tokens
+        input_ids = self.encode(query) if isinstance(query, str) else query.to(self.device)
+        max_new = self.gen_kwargs["max_new_tokens"]
+        eos = self.eos_token_ids
+        n_draft = self._draft_len(num_draft)
+        drafter = draft if draft is not None else lookup_draft
+        prior = [kv.prefill_ids[0]] if getattr(kv, "prefill_ids", None) is not None else []
+        history = torch.cat(prior + [input_ids[0]])
+        stats = {"steps": 0, "tokens": 0, "drafted": 0, "accepted": 0}
+        logits = self.model(input_ids, past_key_values=kv, use_cache=True).logits[:, -1]
+        out = [int(logits.argmax(-1))]          # invariant: the cache holds the query and out[:-1]
+        while len(out) < max_new and out[-1] not in eos:
+            room = max_new - len(out)
+            last = torch.tensor([out[-1]], dtype=torch.long, device=self.device)
+            history = torch.cat([history, last])
+            d_ids = history[:0]
+            if n_draft > 0 and room > 1:
+                d_ids = drafter(history, min(n_draft, room - 1)).reshape(-1)[:min(n_draft, room - 1)].to(self.device)
+            d = int(d_ids.shape[0])
+            stats["steps"] += 1
+            stats["drafted"] += d
+            if d == 0:      # nothing to verify: the plain decode step
+                out.append(int(self.model(last[None], past_key_values=kv, use_cache=True).logits[:, -1].argmax(-1)))
+                stats["tokens"] += 1
+                continue
+            cur = torch.cat([last, d_ids])[None]
+            pos = torch.arange(kv._seen_tokens, kv._seen_tokens + d + 1, device=self.device)[None]
+            with kv.verifying():
+                argmax = self.model(cur, past_key_values=kv, use_cache=True, position_ids=pos).logits[0].argmax(-1)
+            a = accept_greedy(d_ids, argmax)
+            new = d_ids[:a].tolist() + [int(argmax[a])]
+            kv.rewind(d - a)                    # the cache holds `last` and the accepted ids
+            stats["accepted"] += a
+            for j, tok in enumerate(new):       # an EOS inside the accepted run ends the answer there
+                if tok in eos:
+                    kv.rewind(a - j)            # (the rows of the ids behind it, and its own, are not part of what generate leaves)
+                    new = new[:j + 1]
+                    break
+            stats["tokens"] += len(new)
+            out += new
+            history = torch.cat([history, torch.tensor(new[:-1], dtype=torch.long, device=history.device)])
+        a_ids = torch.tensor(out[:-1], dtype=torch.long, device=self.device)[None]
+        if not update_cache:
+            kv.slice(seen_token_prev)
+        elif kv.prefill_ids is not None:
+            kv.prefill_ids = torch.cat([kv.prefill_ids, input_ids, a_ids], dim=1)
+        res = a_ids if return_ids else self.decode(a_ids)
+        return (res, stats) if return_stats else res
+
     @_on_model_device
     @torch.inference_mode()
     def generate_batch(self, queries, kv, return_ids: bool = False, keep: Optional[int] = None) -> list:
