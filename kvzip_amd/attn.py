@@ -51,6 +51,17 @@ def register_attention_interface():
     AttentionInterface.register("kvzip_hip", dense_causal_attention)
 
 
+def _rows_out(self, attn: torch.Tensor, bsz: int, q_len: int):
+    """What the forward returns for a cache hook's ``[Hkv, q, G, D]`` (= ``[Hkv*q, G, D]``) rows: ``o_proj`` of ``[b, q, H*D]``."""
+    n_kv = self.config.num_key_value_heads
+    return self.o_proj(attn.view(bsz, n_kv, q_len, -1, self.head_dim).transpose(1, 2).reshape(bsz, q_len, -1).contiguous()), None
+
+
+def _step_out(self, attn: torch.Tensor, bsz: int):
+    """... for the ``[B, Hkv, G, D]`` rows of a batched decode step: ``o_proj`` of ``[B, 1, H*D]``."""
+    return self.o_proj(attn.view(bsz, 1, -1)), None
+
+
 def llama_qwen_attn_forward(self, hidden_states: torch.Tensor,
                             position_embeddings: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                             attention_mask: Optional[torch.Tensor] = None, past_key_values=None, **kwargs):
@@ -73,43 +84,29 @@ def llama_qwen_attn_forward(self, hidden_states: torch.Tensor,
     kv = past_key_values
     # forked decode (kvcache.ForkedCache): B queries share one pruned cache; one of the two places a batch > 1 is taken
     if getattr(kv, "layout", None) == "fork":
-        n_kv = self.config.num_key_value_heads
         if q_len == 1 and bsz == kv.n_branches:
-            attn = kv.update_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling)  # [B, Hkv, G, D]
-            return self.o_proj(attn.view(bsz, 1, -1)), None
-        attn = kv.first_step(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling)         # [Hkv, q, G, D]
-        attn_output = attn.view(bsz, n_kv, q_len, -1, self.head_dim).transpose(1, 2).reshape(bsz, q_len, -1).contiguous()
-        return self.o_proj(attn_output), None
+            return _step_out(self, kv.update_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling), bsz)
+        return _rows_out(self, kv.first_step(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling), bsz, q_len)
     # batched decode (kvcache.CacheBatch): one token for each of B independent pruned caches; the other place a batch > 1 is taken
     if getattr(kv, "layout", None) == "multi":
         if bsz == 1 and getattr(kv, "_packed", None) is not None:
             # packed first step: the query tokens of the selected caches back to back in one batch-1 pass
-            n_kv = self.config.num_key_value_heads
-            attn = kv.first_step(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling)     # [Hkv, q, G, D]
-            attn_output = attn.view(bsz, n_kv, q_len, -1, self.head_dim).transpose(1, 2).reshape(bsz, q_len, -1).contiguous()
-            return self.o_proj(attn_output), None
+            return _rows_out(self, kv.first_step(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling), bsz, q_len)
         if not (q_len == 1 and bsz == kv.n_caches):
             from . import ops
             raise ops.KvzError(f"cache batch: a forward pass over a CacheBatch is one decode step of its {kv.n_caches} caches (got batch "
                                f"{bsz}, {q_len} positions): first steps run at batch 1 on each cache's own path")
-        attn = kv.update_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling)      # [B, Hkv, G, D]
-        return self.o_proj(attn.view(bsz, 1, -1)), None
+        return _step_out(self, kv.update_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling), bsz)
     # generation step on a pruned slack-layout cache: update + prepare + attend in one launch (bit-identical result)
     if (q_len == 1 and getattr(kv, "pruned", None) and not getattr(kv, "get_score", None)
             and getattr(kv, "layout", None) == "slack" and hasattr(kv, "update_attend")):
-        attn = kv.update_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling)
-        n_kv = self.config.num_key_value_heads
-        attn_output = attn.view(bsz, n_kv, q_len, -1, self.head_dim).transpose(1, 2).reshape(bsz, q_len, -1).contiguous()
-        return self.o_proj(attn_output), None
+        return _rows_out(self, kv.update_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling), bsz, q_len)
     # verify step of speculative decoding (only inside `with kv.verifying():`): update + prepare + attend for the t drafted positions
     # in one call that reads the kept rows once
     if (q_len > 1 and bsz == 1 and getattr(kv, "_verifying", False) and getattr(kv, "pruned", None)
             and not getattr(kv, "get_score", None) and getattr(kv, "layout", None) == "slack"
             and q_len * (query_states.shape[1] // key_states.shape[1]) <= 64):
-        attn = kv.verify_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling)  # [Hkv*q_len, G, D]
-        n_kv = self.config.num_key_value_heads
-        attn_output = attn.view(bsz, n_kv, q_len, -1, self.head_dim).transpose(1, 2).reshape(bsz, q_len, -1).contiguous()
-        return self.o_proj(attn_output), None
+        return _rows_out(self, kv.verify_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling), bsz, q_len)
     if kv is not None:
         key_states, value_states = kv.update(key_states, value_states, self.layer_idx)
 
@@ -126,9 +123,7 @@ def llama_qwen_attn_forward(self, hidden_states: torch.Tensor,
         pass
     elif getattr(kv, "pruned", None):     # attention with the pruned cache (attention/attn.py:56-73)
         q, k, v, info = kv.prepare(query_states.contiguous(), key_states, value_states, self.layer_idx)
-        attn = kv.attend(q, k, v, info, causal=True, softmax_scale=self.scaling)      # [Hkv*q_len, G, D]
-        n_kv = self.config.num_key_value_heads
-        attn_output = attn.view(bsz, n_kv, q_len, -1, self.head_dim).transpose(1, 2)  # [b, q, Hkv, G, D]
+        return _rows_out(self, kv.attend(q, k, v, info, causal=True, softmax_scale=self.scaling), bsz, q_len)
     else:
         attn_output, _ = dense_causal_attention(self, query_states, key_states, value_states, None,
                                                 scaling=self.scaling)

@@ -496,17 +496,25 @@ class EvictCache(_CacheBase):
                                softmax_scale=softmax_scale, workspace=ws,
                                k_len_offset=info["k_len_offset"], meta_host=info.get("meta_host"))
 
+    def _workspace(self, attr: str, key, make, args, need: int = 0, keep: Optional[int] = None) -> torch.Tensor:
+        """Kernel scratch ``make(*args)`` from the lazily created dict ``attr`` of this cache: made at the first request for ``key``,
+        and with a ``need`` again when the one at hand holds fewer elements or lives on another device than ``args[-1]``; a new key
+        that finds more than ``keep`` others drops them all."""
+        cache = getattr(self, attr, None)
+        if cache is None:
+            cache = {}
+            setattr(self, attr, cache)
+        ws = cache.get(key)
+        if ws is None or (need and (ws.numel() < need or ws.device != torch.device(args[-1]))):
+            if ws is None and keep is not None and len(cache) > keep:
+                cache.clear()
+            ws = cache[key] = make(*args)
+        return ws
+
     def _attn_workspace(self, q_len: int, dim: int, device) -> torch.Tensor:
         """Zero-initialised scratch of the attention kernel, one per query length (its size does not depend on the key lengths)."""
-        cache = getattr(self, "_attn_ws_cache", None)
-        if cache is None:
-            cache = self._attn_ws_cache = {}
-        ws = cache.get((q_len, dim))
-        if ws is None:
-            if len(cache) > 4:
-                cache.clear()
-            ws = cache[(q_len, dim)] = ops.attn_workspace(self.n_heads_kv, self.n_group_kv, q_len, dim, device)
-        return ws
+        return self._workspace("_attn_ws_cache", (q_len, dim), ops.attn_workspace, (self.n_heads_kv, self.n_group_kv, q_len, dim, device),
+                               keep=4)
 
     def _meta_host(self, layer_idx: int):
         """Head segments of a layer as kernel arguments (host copy made at prune / slack growth), or None."""
@@ -577,15 +585,9 @@ class EvictCache(_CacheBase):
 
     def _spec_workspace(self, t: int, dim: int, device) -> torch.Tensor:
         """Scratch of the verify step, one per number of 16-row tiles (its size depends on nothing else that changes between steps)."""
-        cache = getattr(self, "_spec_ws_cache", None)
-        if cache is None:
-            cache = self._spec_ws_cache = {}
-        key = ((t * self.n_group_kv + 15) // 16, dim)
         need = int(ops._lib.load().kvz_spec_attn_workspace_bytes(t, self.n_heads_kv, self.n_group_kv, dim))
-        ws = cache.get(key)
-        if ws is None or ws.numel() < need or ws.device != torch.device(device):
-            ws = cache[key] = ops.spec_attn_workspace(t, self.n_heads_kv, self.n_group_kv, dim, device)
-        return ws
+        return self._workspace("_spec_ws_cache", ((t * self.n_group_kv + 15) // 16, dim), ops.spec_attn_workspace,
+                               (t, self.n_heads_kv, self.n_group_kv, dim, device), need=need)
 
     def rewind(self, n: int) -> None:
         """Take back the last ``n`` appended positions (the rejected tail of a verify step): a host-side decrement of every layer's
@@ -710,7 +712,75 @@ def plan_branch_reorder(parents: Sequence[int], n_slots: int) -> Tuple[List[int]
     return slots, pairs
 
 
-class ForkedCache:
+def pruned_slack(c):
+    """Whether (truthy or falsy) the ``EvictCache`` ``c`` is pruned into the flat slack layout: what a fork shares, a batch appends to and a verify
+    step rewinds."""
+    return c.pruned and c.info.get("flatten") and c.layout == "slack"
+
+
+def _decode_rows(key_states: torch.Tensor, value_states: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The new K and V rows ``[B, Hkv, 1, D]`` of a batched decode step as its kernels read them: unit stride along D, batch and head
+    strides multiples of 8 elements.  Copied only when the strides require it."""
+    (kb, kh, _, kd), (vb, vh, _, vd) = key_states.stride(), value_states.stride()
+    if kd != 1 or vd != 1 or kb % 8 or kh % 8 or vb % 8 or vh % 8:
+        return key_states.contiguous(), value_states.contiguous()
+    return key_states, value_states
+
+
+class _Slots:
+    """The slot protocol ``ForkedCache`` (a slot is a branch) and ``CacheBatch`` (a slot is a member) share: ``active`` says which
+    slots are live (its length is the slot count), ``retire`` ends one, and ``select_packed`` names the slots whose query tokens the
+    next forward pass carries back to back (``_packed``; cleared after the last layer's call).  ``_nouns`` words the messages."""
+
+    _nouns: Tuple[str, str, str, str, str]   # who raises, its short name, a slot, several slots, where a slot's rows land
+    active: List[bool]
+    _packed: Optional[Tuple[List[int], List[int]]] = None   # (slots, lengths) of the next forward pass
+
+    def select_packed(self, slots: Sequence[int], lengths: Sequence[int]) -> None:
+        """The next forward pass carries the queries of ``slots`` (distinct, live) back to back, ``lengths[i]`` tokens of ``slots[i]``
+        each: every layer's ``first_step`` then takes ``sum(lengths)`` positions.  Cleared after the last layer's call."""
+        who, short, one, many, home = self._nouns
+        slots, lengths = [int(b) for b in slots], [int(n) for n in lengths]
+        if len(slots) != len(lengths):
+            raise ops.KvzError(f"{who}: select_packed got {len(slots)} {many} and {len(lengths)} lengths")
+        if not slots:
+            raise ops.KvzError(f"{who}: select_packed needs at least one {one}")
+        if len(set(slots)) != len(slots):
+            raise ops.KvzError(f"{who}: select_packed names a {one} twice ({slots}): its rows would land in one {home} twice")
+        for b, n in zip(slots, lengths):
+            if not 0 <= b < len(self.active):
+                raise ops.KvzError(f"{who}: select_packed: no {one} {b} (the {short} has {len(self.active)})")
+            if not self.active[b]:
+                raise ops.KvzError(f"{who}: select_packed: {one} {b} is retired")
+            if n < 0:
+                raise ops.KvzError(f"{who}: select_packed: {one} {b} has a negative length {n}")
+        self._packed = (slots, lengths)
+
+    def retire(self, b: int) -> None:
+        """Slot ``b`` is finished (EOS, token budget): later decode steps skip it (no write, zero output rows)."""
+        self.active[b] = False
+
+    def _packing(self, query_states: torch.Tensor):
+        """The selected packing for ``[1, H, T, D]`` queries -> ``(slots, lengths, order, cu)``: ``order`` lists the slots in packing
+        order, then those that take no part; ``cu[i] .. cu[i + 1]`` are the positions of ``order[i]`` (empty runs at the end)."""
+        slots, lengths = self._packed
+        bsz, T = query_states.shape[0], query_states.shape[2]
+        if bsz != 1 or T != sum(lengths):
+            raise ops.KvzError(f"{self._nouns[0]}: the packed first step takes [1, H, {sum(lengths)}, D] queries, the lengths "
+                               f"{lengths} of {self._nouns[3]} {slots} back to back (got batch {bsz}, {T} positions)")
+        order = slots + [b for b in range(len(self.active)) if b not in slots]
+        cu = [0]
+        for n in lengths:
+            cu.append(cu[-1] + n)
+        cu += [T] * (len(self.active) - len(slots))
+        return slots, lengths, order, cu
+
+    def _packing_done(self, layer_idx: int) -> None:
+        if layer_idx == self.n_layers - 1:
+            self._packed = None
+
+
+class ForkedCache(_Slots):
     """``n_branches`` concurrent queries over ONE pruned slack-layout ``EvictCache`` (``EvictCache.fork``; no reference counterpart:
     batch is 1 there).  The branches share the base cache's flat K,V read-only - its rows, segment starts and lengths as they were at
     the fork, rows a multi-turn ``update_cache=True`` appended before it included - and every branch owns a private tail per layer
@@ -730,13 +800,14 @@ class ForkedCache:
     Beam search: ``reorder(parents)`` makes "hypothesis i continues from slot ``parents[i]``" true between two decode steps by copying
     whole tails between slots (``kvz_fork_branch_copy``: survivors stay where they are, one copy per dropped hypothesis)."""
 
+    _nouns = ("forked cache", "fork", "branch", "branches", "tail")
     _closed = False   # commit() sets it on the instance: one branch's rows now belong to the base and every later hook raises
 
     @staticmethod
     def check_base(base, n_branches: int) -> None:
         """Raise ``KvzError`` unless ``base`` can be forked into ``n_branches`` (what ``__init__`` asks; a caller that appends rows to
         the base before it forks asks first, so that a refusal leaves the base as it was)."""
-        if not (isinstance(base, EvictCache) and base.pruned and base.info.get("flatten") and base.layout == "slack"):
+        if not (isinstance(base, EvictCache) and pruned_slack(base)):
             raise ops.KvzError("fork: needs a pruned EvictCache in the slack layout")
         G = base.n_group_kv
         if n_branches < 1 or n_branches > ops.FORK_MAX_BRANCHES or n_branches * G > ops.FORK_MAX_ROWS:
@@ -769,7 +840,7 @@ class ForkedCache:
         self.tail_len = [[0] * self.n_branches for _ in range(self.n_layers)]
         self.active = [True] * self.n_branches
         self._branch = 0
-        self._packed: Optional[Tuple[List[int], List[int]]] = None   # (branches, lengths) of the next forward pass (select_packed)
+        self._packed = None
         self._ws = None
 
     # -- bookkeeping ---------------------------------------------------------------------------------
@@ -780,29 +851,6 @@ class ForkedCache:
         """The branch the next ``first_step`` calls belong to."""
         assert 0 <= b < self.n_branches
         self._branch = int(b)
-
-    def select_packed(self, branches: Sequence[int], lengths: Sequence[int]) -> None:
-        """The next forward pass carries the queries of ``branches`` (distinct, live) back to back, ``lengths[i]`` tokens of
-        ``branches[i]`` each: every layer's ``first_step`` then takes ``sum(lengths)`` positions.  Cleared after the last layer's call."""
-        branches, lengths = [int(b) for b in branches], [int(n) for n in lengths]
-        if len(branches) != len(lengths):
-            raise ops.KvzError(f"forked cache: select_packed got {len(branches)} branches and {len(lengths)} lengths")
-        if not branches:
-            raise ops.KvzError("forked cache: select_packed needs at least one branch")
-        if len(set(branches)) != len(branches):
-            raise ops.KvzError(f"forked cache: select_packed names a branch twice ({branches}): its rows would land in one tail twice")
-        for b, n in zip(branches, lengths):
-            if not 0 <= b < self.n_branches:
-                raise ops.KvzError(f"forked cache: select_packed: no branch {b} (the fork has {self.n_branches})")
-            if not self.active[b]:
-                raise ops.KvzError(f"forked cache: select_packed: branch {b} is retired")
-            if n < 0:
-                raise ops.KvzError(f"forked cache: select_packed: branch {b} has a negative length {n}")
-        self._packed = (branches, lengths)
-
-    def retire(self, b: int) -> None:
-        """Branch ``b`` is finished (EOS, token budget): later decode steps skip it (no write, zero output rows)."""
-        self.active[b] = False
 
     def _check(self, layer_idx: int) -> None:
         base = self.base
@@ -932,27 +980,17 @@ class ForkedCache:
         return ops.attn_merge_lse(o1, l1, o2, l2, out=o1)
 
     def _first_step_packed(self, query_states, key_states, value_states, layer_idx, softmax_scale):
-        branches, lengths = self._packed
-        bsz, _, T, D = query_states.shape
-        if bsz != 1 or T != sum(lengths):
-            raise ops.KvzError(f"forked cache: the packed first step takes [1, H, {sum(lengths)}, D] queries, the lengths "
-                               f"{lengths} of branches {branches} back to back (got batch {bsz}, {T} positions)")
+        branches, lengths, order, cu = self._packing(query_states)
+        D = query_states.shape[-1]
         tlen = self.tail_len[layer_idx]
         tk, tv = self._tails(layer_idx, max(tlen[b] + n for b, n in zip(branches, lengths)), D)
         o, lse = ops.flash_fwd_ragged(query_states, self._k[layer_idx], self._v[layer_idx], self._starts[layer_idx],
                                       self._lens[layer_idx], causal=False, softmax_scale=softmax_scale)
-        # the runs of positions in packing order, then the branches that take no part (empty runs at the end)
-        order = branches + [b for b in range(self.n_branches) if b not in branches]
-        cu = [0]
-        for n in lengths:
-            cu.append(cu[-1] + n)
-        cu += [T] * (self.n_branches - len(branches))
         ops.fork_prefill_tail(query_states, cu, tk, tv, tlen, key_states, value_states, o, lse, softmax_scale=softmax_scale, out=o,
                               branches=order)
         for b, n in zip(branches, lengths):
             tlen[b] += n
-        if layer_idx == self.n_layers - 1:
-            self._packed = None
+        self._packing_done(layer_idx)
         return o
 
     def update_attend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
@@ -965,9 +1003,7 @@ class ForkedCache:
             raise ops.KvzError(f"forked cache: a decode step takes [{self.n_branches}, H, 1, D] queries (got batch {B}, {q_len} positions)")
         lens = self.tail_len[layer_idx]
         tk, tv = self._tails(layer_idx, max(lens) + 1, D)
-        if key_states.stride(-1) != 1 or value_states.stride(-1) != 1 or key_states.stride(0) % 8 or key_states.stride(1) % 8 \
-                or value_states.stride(0) % 8 or value_states.stride(1) % 8:
-            key_states, value_states = key_states.contiguous(), value_states.contiguous()
+        key_states, value_states = _decode_rows(key_states, value_states)
         if self._ws is None or self._ws[0] != D:
             self._ws = (D, ops.fork_attn_workspace(B, self.n_heads_kv, self.n_group_kv, D, self.device))
         q = query_states.reshape(B, self.n_heads_kv, self.n_group_kv, D).contiguous()
@@ -981,7 +1017,7 @@ class ForkedCache:
         return out
 
 
-class CacheBatch:
+class CacheBatch(_Slots):
     """Several INDEPENDENT pruned slack-layout ``EvictCache`` objects decoding together, one token each per step (no reference
     counterpart: batch is 1 there).  Several users, each with an own compressed context: one decode step of all live members is one
     attention launch per layer (``kvz_multi_attn_append``), whose work items are cut from the sum of ALL members' head lengths.
@@ -1000,6 +1036,8 @@ class CacheBatch:
         exactly as after its own ``update`` + ``prepare`` + ``attend``.
     Without a packing, first steps (``q_len > 1``) do not go through the batch: they run at batch 1 on each member's own path."""
 
+    _nouns = ("cache batch", "batch", "member", "members", "slack")
+
     def __init__(self, caches):
         caches = list(caches)
         if not caches:
@@ -1008,9 +1046,9 @@ class CacheBatch:
             if not isinstance(c, EvictCache):
                 raise ops.KvzError(f"cache batch: members are pruned EvictCache objects in the slack layout (got {type(c).__name__}: "
                                    "forks share one cache - kvz_fork_attn_append is their launch - and a RetainCache never evicts)")
-            if not (c.pruned and c.info.get("flatten")):
-                raise ops.KvzError("cache batch: a member is not pruned yet (prune() first)")
-            if c.layout != "slack":
+            if not pruned_slack(c):
+                if not (c.pruned and c.info.get("flatten")):
+                    raise ops.KvzError("cache batch: a member is not pruned yet (prune() first)")
                 raise ops.KvzError("cache batch: a member is in the packed layout (its segments move with every appended token); "
                                    "layout='slack' is what the batched decode step appends to")
         if len({id(c) for c in caches}) != len(caches):
@@ -1034,52 +1072,30 @@ class CacheBatch:
         self.device, self.dtype = c0.device, c0.dtype
         self.pruned, self.get_score, self.layout = True, False, "multi"
         self.active = [True] * B
-        self._tables: Optional[List[ops.MultiTable]] = None   # per layer; valid while the members' layout epochs are _epochs
-        self._epochs: Optional[Tuple[int, ...]] = None
+        self._packed = None
+        self._tables = {}   # (members' layout epochs, member order) -> the tables per layer (_table)
         self._ws = None
-        self._packed: Optional[Tuple[List[int], List[int]]] = None   # (members, lengths) of the next forward pass (select_packed)
-        self._ptables = None                                  # the tables in packing order, valid for _pkey = (epochs, order)
-        self._pkey = None
         self._pws = None
 
     def get_seq_length(self, layer_idx: Optional[int] = 0) -> int:
         return max(c.get_seq_length(layer_idx) for c in self.caches)
 
-    def select_packed(self, members: Sequence[int], lengths: Sequence[int]) -> None:
-        """The next forward pass carries the queries of ``members`` (distinct, live) back to back, ``lengths[i]`` tokens of
-        ``members[i]`` each: every layer's ``first_step`` then takes ``sum(lengths)`` positions.  Cleared after the last layer's call."""
-        members, lengths = [int(b) for b in members], [int(n) for n in lengths]
-        if len(members) != len(lengths):
-            raise ops.KvzError(f"cache batch: select_packed got {len(members)} members and {len(lengths)} lengths")
-        if not members:
-            raise ops.KvzError("cache batch: select_packed needs at least one member")
-        if len(set(members)) != len(members):
-            raise ops.KvzError(f"cache batch: select_packed names a member twice ({members}): its rows would land in one slack twice")
-        for b, n in zip(members, lengths):
-            if not 0 <= b < self.n_caches:
-                raise ops.KvzError(f"cache batch: select_packed: no member {b} (the batch has {self.n_caches})")
-            if not self.active[b]:
-                raise ops.KvzError(f"cache batch: select_packed: member {b} is retired")
-            if n < 0:
-                raise ops.KvzError(f"cache batch: select_packed: member {b} has a negative length {n}")
-        self._packed = (members, lengths)
-
-    def retire(self, b: int) -> None:
-        """Member ``b`` is finished (EOS, token budget): later steps skip it (no write, no work item, zero output rows)."""
-        self.active[b] = False
-
-    def _packed_table(self, layer_idx: int, order: List[int]) -> "ops.MultiTable":
-        """The layer's table with the members in ``order`` (the runs of a packing lie in the order it names its members)."""
-        key = (tuple(c._layout_epoch for c in self.caches), tuple(order))
-        if self._ptables is None or key != self._pkey:
+    def _table(self, layer_idx: int, order: Optional[Tuple[int, ...]] = None) -> "ops.MultiTable":
+        """The layer's table with the members in ``order`` (None: as the batch lists them, what a decode step takes; the runs of a
+        packing lie in the order it names its members).  Built for all layers at an order's first use and kept until a member's
+        layout changes, which drops every order's tables: the decode order and a packing order live side by side."""
+        key = (tuple([c._layout_epoch for c in self.caches]), order)
+        tables = self._tables.get(key)
+        if tables is None:
+            if any(k[0] != key[0] for k in self._tables) or len(self._tables) > 4:
+                self._tables.clear()
             Hkv = self.n_heads_kv
-            cs = [self.caches[b] for b in order]
+            cs = self.caches if order is None else [self.caches[b] for b in order]
             metas = [c.info["meta_host"] for c in cs]
-            self._ptables = [ops.MultiTable([c.key_cache[l] for c in cs], [c.value_cache[l] for c in cs],
-                                            [list(m[l][:Hkv]) for m in metas], [list(m[l][Hkv:2 * Hkv]) for m in metas],
-                                            [c.slack for c in cs]) for l in range(self.n_layers)]
-            self._pkey = key
-        return self._ptables[layer_idx]
+            tables = self._tables[key] = [ops.MultiTable([c.key_cache[l] for c in cs], [c.value_cache[l] for c in cs],
+                                                         [list(m[l][:Hkv]) for m in metas], [list(m[l][Hkv:2 * Hkv]) for m in metas],
+                                                         [c.slack for c in cs]) for l in range(self.n_layers)]
+        return tables[layer_idx]
 
     def first_step(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
                    softmax_scale: Optional[float] = None) -> torch.Tensor:
@@ -1090,15 +1106,10 @@ class CacheBatch:
         if self._packed is None:
             raise ops.KvzError("cache batch: first_step needs a packing (select_packed): without one, first steps run at batch 1 on "
                                "each cache's own path")
-        members, lengths = self._packed
-        bsz, _, T, D = query_states.shape
-        if bsz != 1 or T != sum(lengths):
-            raise ops.KvzError(f"cache batch: the packed first step takes [1, H, {sum(lengths)}, D] queries, the lengths "
-                               f"{lengths} of members {members} back to back (got batch {bsz}, {T} positions)")
-        for b, n in zip(members, lengths):
-            c = self.caches[b]
-            if not (c.pruned and c.info.get("flatten") and c.layout == "slack"):
-                raise ops.KvzError("cache batch: a member is no longer a pruned slack-layout cache")
+        members, lengths, order, cu = self._packing(query_states)
+        T, D = query_states.shape[2], query_states.shape[3]
+        if not all(pruned_slack(self.caches[b]) for b in members):
+            raise ops.KvzError("cache batch: a member is no longer a pruned slack-layout cache")
         offsets = []
         for b, n in zip(members, lengths):
             c = self.caches[b]
@@ -1106,14 +1117,8 @@ class CacheBatch:
             if n and off + n > c.slack:
                 c._grow_slack(off + n)      # (bumps the member's layout epoch: the table below is rebuilt)
             offsets.append(off)
-        # the runs of positions in packing order, then the members that take no part (empty runs at the end)
-        order = members + [b for b in range(self.n_caches) if b not in members]
-        cu = [0]
-        for n in lengths:
-            cu.append(cu[-1] + n)
-        cu += [T] * (self.n_caches - len(members))
-        offsets += [0] * (self.n_caches - len(members))
-        table = self._packed_table(layer_idx, order)
+        offsets += [0] * (self.n_caches - len(members))     # (the members that take no part: empty runs at the end)
+        table = self._table(layer_idx, tuple(order))
         if self._pws is None or self._pws[0] != (T, D):
             self._pws = ((T, D), ops.multi_prefill_workspace(T, self.n_caches, self.n_heads_kv, self.n_group_kv, D, self.device))
         out = ops.multi_prefill(query_states, cu, table, offsets, key_states, value_states, softmax_scale=softmax_scale,
@@ -1124,20 +1129,8 @@ class CacheBatch:
                 c.info["offset"][layer_idx] = off + n
                 if layer_idx == 0:
                     c._seen_tokens += n
-        if layer_idx == self.n_layers - 1:
-            self._packed = None
+        self._packing_done(layer_idx)
         return out
-
-    def _table(self, layer_idx: int) -> "ops.MultiTable":
-        epochs = tuple(c._layout_epoch for c in self.caches)
-        if self._tables is None or epochs != self._epochs:
-            Hkv = self.n_heads_kv
-            metas = [c.info["meta_host"] for c in self.caches]
-            self._tables = [ops.MultiTable([c.key_cache[l] for c in self.caches], [c.value_cache[l] for c in self.caches],
-                                           [list(m[l][:Hkv]) for m in metas], [list(m[l][Hkv:2 * Hkv]) for m in metas],
-                                           [c.slack for c in self.caches]) for l in range(self.n_layers)]
-            self._epochs = epochs
-        return self._tables[layer_idx]
 
     def update_attend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
                       softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1153,16 +1146,14 @@ class CacheBatch:
             if not live:
                 offsets.append(-1)
                 continue
-            if not (c.pruned and c.info.get("flatten") and c.layout == "slack"):
+            if not pruned_slack(c):
                 raise ops.KvzError("cache batch: a member is no longer a pruned slack-layout cache")
             off = c.info["offset"][layer_idx]
             if off + 1 > c.slack:
                 c._grow_slack(off + 1)      # (bumps the member's layout epoch: the table below is rebuilt)
             offsets.append(off)
         table = self._table(layer_idx)
-        if key_states.stride(-1) != 1 or value_states.stride(-1) != 1 or key_states.stride(0) % 8 or key_states.stride(1) % 8 \
-                or value_states.stride(0) % 8 or value_states.stride(1) % 8:
-            key_states, value_states = key_states.contiguous(), value_states.contiguous()
+        key_states, value_states = _decode_rows(key_states, value_states)
         if self._ws is None or self._ws[0] != D:
             self._ws = (D, ops.multi_attn_workspace(B, self.n_heads_kv, self.n_group_kv, D, self.device))
         q = query_states.reshape(B, self.n_heads_kv, self.n_group_kv, D).contiguous()
@@ -1243,5 +1234,5 @@ class RetainCache(_CacheBase):
         return query_states, k_flat.view(-1, 1, dim), v_flat.view(-1, 1, dim), info
 
     attend = EvictCache.attend
-    _attn_workspace = EvictCache._attn_workspace
+    _workspace, _attn_workspace = EvictCache._workspace, EvictCache._attn_workspace
     _attn_ws = None

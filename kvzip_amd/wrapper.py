@@ -23,7 +23,8 @@ from typing import List, Optional, Tuple, Union
 
 import torch
 
-from .kvcache import CacheBatch, EvictCache, ForkedCache, RetainCache
+from . import ops
+from .kvcache import CacheBatch, EvictCache, ForkedCache, RetainCache, pruned_slack
 from .monkeypatch import replace_attn
 from .ops import KvzError
 from .template import template
@@ -140,6 +141,10 @@ class ModelKVzip:
             raise ValueError("no tokenizer: pass token-id tensors instead of text")
         return self.tokenizer.encode(text, add_special_tokens=False, return_tensors="pt").to(self.device)
 
+    def _ids(self, query: Union[str, torch.Tensor]) -> torch.Tensor:
+        """Text or token ids -> ``[1, n]`` ids on the model's device."""
+        return self.encode(query) if isinstance(query, str) else query.to(self.device)
+
     def decode(self, input_ids: torch.Tensor) -> str:
         if input_ids.dim() == 2:
             input_ids = input_ids[0]
@@ -192,9 +197,7 @@ class ModelKVzip:
     def prefill(self, ctx_ids: Union[str, torch.Tensor], prefill_chunk_size: int = 16000, load_score: bool = False,
                 do_score: bool = True):
         """Chunked prefill of the KV cache, then KV importance scoring."""
-        if isinstance(ctx_ids, str):
-            ctx_ids = self.encode(ctx_ids)
-        ctx_ids = ctx_ids.to(self.device)
+        ctx_ids = self._ids(ctx_ids)
         prefill_ids = torch.cat([self.sys_prompt_ids, ctx_ids], dim=1)
         evict_range = (self.sys_prompt_ids.shape[1], prefill_ids.shape[1])
         kv = self._init_kv(evict_range=evict_range)  # the system prompt is never evicted
@@ -300,7 +303,7 @@ class ModelKVzip:
         (multi-turn)."""
         kv = self._init_kv(kv=kv)
         seen_token_prev = kv._seen_tokens
-        input_ids = self.encode(query) if isinstance(query, str) else query.to(self.device)
+        input_ids = self._ids(query)
         out_ids = []
         cur = input_ids
         for _ in range(self.gen_kwargs["max_new_tokens"]):
@@ -313,18 +316,32 @@ class ModelKVzip:
         # the reference drops the last generated token (model/wrapper.py:277: output[:, len(input_ids):-1]): it is the
         # terminating EOS (or the token that hit max_new_tokens) and its KV was never written to the cache
         a_ids = torch.cat(out_ids, dim=1)[:, :-1]
-        if not update_cache:
-            kv.slice(seen_token_prev)
-        elif kv.prefill_ids is not None:
-            kv.prefill_ids = torch.cat([kv.prefill_ids, input_ids, a_ids], dim=1)
+        self._end_turn(kv, update_cache, seen_token_prev, input_ids, a_ids)
         return a_ids if return_ids else self.decode(a_ids)
+
+    @staticmethod
+    def _end_turn(kv, update_cache: bool, seen_prev: Optional[int], q_ids: torch.Tensor, a_ids: torch.Tensor) -> None:
+        """How a turn leaves its cache: sliced back to the ``seen_prev`` tokens it held before, or (``update_cache``, multi-turn)
+        keeping the rows of query and answer, with ``prefill_ids`` grown by them."""
+        if not update_cache:
+            kv.slice(seen_prev)
+        elif kv.prefill_ids is not None:
+            kv.prefill_ids = torch.cat([kv.prefill_ids, q_ids, a_ids], dim=1)
+
+    def _group(self) -> int:
+        """Query heads per KV head (G)."""
+        return self.config.num_attention_heads // self.config.num_key_value_heads
+
+    def _fork_wave(self) -> int:
+        """Branches of one forked decode wave: ``fork_max_branches`` within what one launch takes."""
+        return max(1, min(self.fork_max_branches, ops.FORK_MAX_BRANCHES, ops.FORK_MAX_ROWS // self._group()))
 
     def _draft_len(self, num_draft: Optional[int] = None) -> int:
         """Drafted tokens per verify step (the step runs t = 1 + draft positions).  The default keeps t*G <= 32 query rows per KV
         head - one block per work item, where the forked decode's step time holds - and a request is capped at t*G <= 64,
         the kernel's limit.  Both come from the forked-decode table, not from a measurement of the verify kernel: a shape that
         tools/spec_decode_bench.py flags as slower than the existing path gets its rule HERE."""
-        G = self.config.num_attention_heads // self.config.num_key_value_heads
+        G = self._group()
         cap = max(0, 64 // G - 1)
         if num_draft is None:
             return max(0, 32 // G - 1)
@@ -346,11 +363,11 @@ class ModelKVzip:
         from .draft import accept_greedy, lookup_draft
         if self.gen_kwargs.get("do_sample", False):
             raise ValueError("generate_speculative is greedy: do_sample=True needs a distribution-preserving acceptance rule, use generate")
-        if not (isinstance(kv, EvictCache) and kv.pruned and kv.info.get("flatten") and kv.layout == "slack"):
+        if not (isinstance(kv, EvictCache) and pruned_slack(kv)):
             raise ValueError("generate_speculative needs a pruned slack-layout EvictCache (the verify step appends to and rewinds the "
                              "slack behind the kept rows): use generate for a dense or packed-layout cache")
         seen_token_prev = kv._seen_tokens
-        input_ids = self.encode(query) if isinstance(query, str) else query.to(self.device)
+        input_ids = self._ids(query)
         max_new = self.gen_kwargs["max_new_tokens"]
         eos = self.eos_token_ids
         n_draft = self._draft_len(num_draft)
@@ -391,10 +408,7 @@ class ModelKVzip:
             out += new
             history = torch.cat([history, torch.tensor(new[:-1], dtype=torch.long, device=history.device)])
         a_ids = torch.tensor(out[:-1], dtype=torch.long, device=self.device)[None]
-        if not update_cache:
-            kv.slice(seen_token_prev)
-        elif kv.prefill_ids is not None:
-            kv.prefill_ids = torch.cat([kv.prefill_ids, input_ids, a_ids], dim=1)
+        self._end_turn(kv, update_cache, seen_token_prev, input_ids, a_ids)
         res = a_ids if return_ids else self.decode(a_ids)
         return (res, stats) if return_stats else res
 
@@ -412,9 +426,8 @@ class ModelKVzip:
         update_cache=True)`` - branch i's rows are appended to the base (``ForkedCache.commit``) and ``prefill_ids`` grows - so that a
         multi-turn conversation goes on from the kept branch; only offered when all queries fit one wave (``KvzError`` otherwise).
         Answers agree with ``generate`` up to the summation order of the attention (an argmax may tie)."""
-        ids = [self.encode(q) if isinstance(q, str) else q.to(self.device) for q in queries]
-        G = self.config.num_attention_heads // self.config.num_key_value_heads
-        wave = max(1, min(self.fork_max_branches, 64 // G))
+        ids = [self._ids(q) for q in queries]
+        wave = self._fork_wave()
         if keep is not None:
             if not 0 <= int(keep) < len(ids):
                 raise KvzError(f"generate_batch: keep={keep} names none of the {len(ids)} queries")
@@ -433,61 +446,73 @@ class ModelKVzip:
         goes to the per-branch loop, which fails on it as it always did.)"""
         return bool(self.fork_packed_first) and all(n > 0 for n in lengths)
 
-    def _generate_wave(self, ids: List[torch.Tensor], kv, keep: Optional[int] = None) -> List[torch.Tensor]:
-        B = len(ids)
-        max_new = self.gen_kwargs["max_new_tokens"]
-        fork = kv.fork(B, tail_capacity=max(x.shape[1] for x in ids) + max_new)
-        base_len = kv.get_seq_length()
-        eos = self.eos_token_ids
+    def _decode_slots(self, cache, first_logits: List[torch.Tensor], first_pos: List[int]) -> List[torch.Tensor]:
+        """The batched token loop of ``generate_batch / generate_samples / generate_multi``: slot b of ``cache`` (a ``ForkedCache`` or
+        a ``CacheBatch``) has run its first step, which left the logits ``first_logits[b]`` (``[1, V]``) and the next position
+        ``first_pos[b]``.  Every slot takes its first token, in slot order; then one forward pass per step gives every live slot
+        one more, the draws again in slot order.  A slot is retired (``cache.retire``) at EOS or at ``max_new_tokens`` while the
+        others go on.  -> the answers ``[1, n_b]`` per slot, the last token dropped (see ``generate``)."""
+        B = len(first_logits)
+        max_new, eos = self.gen_kwargs["max_new_tokens"], self.eos_token_ids
         out_ids: List[List[torch.Tensor]] = [[] for _ in range(B)]
         cur = torch.zeros((B, 1), dtype=torch.long, device=self.device)
-        pos = torch.zeros((B, 1), dtype=torch.long, device=self.device)
+        pos = torch.tensor(first_pos, dtype=torch.long, device=self.device).view(B, 1)
         live = [True] * B
 
-        def take(b, nxt):   # the token branch b has just produced; retire the branch at EOS / the token budget
+        def take(b, logits):   # the token slot b produces from its logits; retire the slot at EOS / the token budget
+            nxt = self.next_token(logits, self.gen_kwargs, self.sample_generator)
             out_ids[b].append(nxt)
             cur[b] = nxt[0]
             if (eos and int(nxt) in eos) or len(out_ids[b]) >= max_new:
                 live[b] = False
-                fork.retire(b)
+                cache.retire(b)
 
+        for b in range(B):
+            take(b, first_logits[b])
+        while any(live):    # one token for every live slot per step
+            logits = self.model(cur, past_key_values=cache, use_cache=True, position_ids=pos).logits[:, -1]
+            pos += 1
+            for b in range(B):
+                if live[b]:
+                    take(b, logits[b:b + 1])
+        return [torch.cat(o, dim=1)[:, :-1] for o in out_ids]
+
+    def _packed_first(self, cache, ids: List[torch.Tensor], starts: List[int]) -> Tuple[List[torch.Tensor], List[int]]:
+        """The first steps of all slots of ``cache`` in ONE forward pass: the queries back to back, query b at the positions from
+        ``starts[b]`` on.  -> what ``_decode_slots`` takes: every slot's logits at its last packed position, and its next position."""
         lens = [x.shape[1] for x in ids]
-        if B >= 2 and self._packs_first_steps(lens):
-            # first steps of all branches in ONE forward pass: the queries back to back, every one at the positions behind the context
-            fork.select_packed(list(range(B)), lens)
-            p = torch.cat([torch.arange(base_len, base_len + n, device=self.device) for n in lens]).unsqueeze(0)
-            logits = self.model(torch.cat(ids, dim=1), past_key_values=fork, use_cache=True, position_ids=p).logits
-            end = 0
-            for b, n in enumerate(lens):   # the next token of a branch comes from its last packed position
-                end += n
-                pos[b] = base_len + n
-                take(b, self.next_token(logits[:, end - 1], self.gen_kwargs, self.sample_generator))
+        cache.select_packed(list(range(len(ids))), lens)
+        p = torch.cat([torch.arange(s, s + n, device=self.device) for s, n in zip(starts, lens)]).unsqueeze(0)
+        logits = self.model(torch.cat(ids, dim=1), past_key_values=cache, use_cache=True, position_ids=p).logits
+        ends = [sum(lens[:b + 1]) for b in range(len(ids))]
+        return [logits[:, e - 1] for e in ends], [s + n for s, n in zip(starts, lens)]
+
+    def _generate_wave(self, ids: List[torch.Tensor], kv, keep: Optional[int] = None) -> List[torch.Tensor]:
+        B = len(ids)
+        fork = kv.fork(B, tail_capacity=max(x.shape[1] for x in ids) + self.gen_kwargs["max_new_tokens"])
+        base_len = kv.get_seq_length()
+        if B >= 2 and self._packs_first_steps([x.shape[1] for x in ids]):
+            first, pos = self._packed_first(fork, ids, [base_len] * B)
         else:
+            first, pos = [], []
             for b in range(B):  # first step of every branch: its query, at batch 1
                 fork.select_branch(b)
                 n = ids[b].shape[1]
                 p = torch.arange(base_len, base_len + n, device=self.device).unsqueeze(0)
-                logits = self.model(ids[b], past_key_values=fork, use_cache=True, position_ids=p).logits[:, -1]
-                pos[b] = base_len + n
-                take(b, self.next_token(logits, self.gen_kwargs, self.sample_generator))
-        while any(live):    # one token for every live branch per step
-            logits = self.model(cur, past_key_values=fork, use_cache=True, position_ids=pos).logits[:, -1]
-            pos += 1
-            for b in range(B):
-                if live[b]:
-                    take(b, self.next_token(logits[b:b + 1], self.gen_kwargs, self.sample_generator))
-        answers = [torch.cat(o, dim=1)[:, :-1] for o in out_ids]
+                # (a copy of the one row: the logits of the whole query need not live until the last branch has run)
+                first.append(self.model(ids[b], past_key_values=fork, use_cache=True, position_ids=p).logits[:, -1].clone())
+                pos.append(base_len + n)
+        answers = self._decode_slots(fork, first, pos)
         if keep is not None:   # the kept branch's tail - its query rows and the rows of its answer - becomes part of the base cache
             fork.commit(keep)
-            if kv.prefill_ids is not None:
-                kv.prefill_ids = torch.cat([kv.prefill_ids, ids[keep], answers[keep]], dim=1)
+            self._end_turn(kv, True, None, ids[keep], answers[keep])
         return answers
 
     def _fork_limit(self, who: str, n: int) -> None:
-        G = self.config.num_attention_heads // self.config.num_key_value_heads
-        if n < 1 or n > 16 or n * G > 64:
-            raise KvzError(f"{who}: {n} branches x {G} query heads per KV head: one forked decode launch takes at most 64 query rows per "
-                           f"KV head (branches x G) and at most 16 branches")
+        G = self._group()
+        if n < 1 or n > ops.FORK_MAX_BRANCHES or n * G > ops.FORK_MAX_ROWS:
+            raise KvzError(f"{who}: {n} branches x {G} query heads per KV head: one forked decode launch takes at most "
+                           f"{ops.FORK_MAX_ROWS} query rows per KV head (branches x G) and at most {ops.FORK_MAX_BRANCHES} branches")
 
     @_on_model_device
     @torch.inference_mode()
@@ -519,7 +544,7 @@ class ModelKVzip:
             raise ValueError(f"generate_beam: num_return={num_return} outside [1, num_beams={B}]")
         ForkedCache.check_base(kv, B)           # (the query's rows go to the base BEFORE the fork: ask now what fork() will ask)
         seen_prev = kv._seen_tokens
-        input_ids = self.encode(query) if isinstance(query, str) else query.to(self.device)
+        input_ids = self._ids(query)
         max_new = self.gen_kwargs["max_new_tokens"]
         eos = set(self.eos_token_ids)
         lp = float(length_penalty)
@@ -572,15 +597,11 @@ class ModelKVzip:
         best = finished[0]
         self.last_beam_hypotheses = [(score, toks) for score, toks, _ in finished]   # best first; every token, the dropped last one included
         answers = [torch.tensor([toks[:-1]], dtype=torch.long, device=self.device).view(1, -1) for _, toks, _ in finished[:int(num_return)]]
-        if not update_cache:
-            kv.slice(seen_prev)
-        else:
-            if best[2] is not None:
-                fork.commit(best[2])
-            elif answers[0].shape[1]:
-                self.model.model(answers[0], past_key_values=kv, use_cache=True)
-            if kv.prefill_ids is not None:
-                kv.prefill_ids = torch.cat([kv.prefill_ids, input_ids, answers[0]], dim=1)
+        if update_cache and best[2] is not None:
+            fork.commit(best[2])
+        elif update_cache and answers[0].shape[1]:
+            self.model.model(answers[0], past_key_values=kv, use_cache=True)
+        self._end_turn(kv, update_cache, seen_prev, input_ids, answers[0])
         out = answers if return_ids else [self.decode(a) for a in answers]
         return out[0] if int(num_return) == 1 else out
 
@@ -597,39 +618,16 @@ class ModelKVzip:
         if n < 1:
             raise ValueError(f"generate_samples: n={n}")
         seen_prev = kv._seen_tokens
-        input_ids = self.encode(query) if isinstance(query, str) else query.to(self.device)
-        G = self.config.num_attention_heads // self.config.num_key_value_heads
-        wave = max(1, min(self.fork_max_branches, 16, 64 // G))
+        input_ids = self._ids(query)
+        wave = self._fork_wave()
         ForkedCache.check_base(kv, min(wave, n))   # (the query's rows go to the base BEFORE the fork: ask now what fork() will ask)
-        max_new = self.gen_kwargs["max_new_tokens"]
-        eos = self.eos_token_ids
         first = self.model(input_ids, past_key_values=kv, use_cache=True).logits[:, -1]
         pos0 = kv.get_seq_length()
         answers: list = []
-        for w0 in range(0, n, wave):
+        for w0 in range(0, n, wave):    # every branch draws its first token from the query's logits
             B = min(wave, n - w0)
-            fork = kv.fork(B, tail_capacity=max(max_new, 1))
-            out_ids: List[List[torch.Tensor]] = [[] for _ in range(B)]
-            cur = torch.zeros((B, 1), dtype=torch.long, device=self.device)
-            pos = torch.full((B, 1), pos0, dtype=torch.long, device=self.device)
-            live = [True] * B
-
-            def take(b, nxt):
-                out_ids[b].append(nxt)
-                cur[b] = nxt[0]
-                if (eos and int(nxt) in eos) or len(out_ids[b]) >= max_new:
-                    live[b] = False
-                    fork.retire(b)
-
-            for b in range(B):
-                take(b, self.next_token(first, self.gen_kwargs, self.sample_generator))
-            while any(live):
-                logits = self.model(cur, past_key_values=fork, use_cache=True, position_ids=pos).logits[:, -1]
-                pos += 1
-                for b in range(B):
-                    if live[b]:
-                        take(b, self.next_token(logits[b:b + 1], self.gen_kwargs, self.sample_generator))
-            answers += [torch.cat(o, dim=1)[:, :-1] for o in out_ids]
+            fork = kv.fork(B, tail_capacity=max(self.gen_kwargs["max_new_tokens"], 1))
+            answers += self._decode_slots(fork, [first] * B, [pos0] * B)
         kv.slice(seen_prev)
         return answers if return_ids else [self.decode(a) for a in answers]
 
@@ -648,7 +646,7 @@ class ModelKVzip:
         takes (16, or ``128 // Hkv``) run in waves.  Answers agree with ``generate`` up to the summation order of the attention (an
         argmax may tie); with ``do_sample=True`` the draws of the sequences interleave."""
         kvs = list(kvs)
-        ids = [self.encode(q) if isinstance(q, str) else q.to(self.device) for q in queries]
+        ids = [self._ids(q) for q in queries]
         if len(ids) != len(kvs):
             raise ValueError(f"generate_multi: {len(ids)} queries for {len(kvs)} caches (one query per cache)")
         wave = max(1, min(self.multi_max_caches, 16, 128 // self.config.num_key_value_heads))
@@ -669,50 +667,17 @@ class ModelKVzip:
         if B == 1:   # (nothing to share: the sequential path)
             return [self.generate(ids[0], kv=kvs[0], update_cache=update_cache, return_ids=True)]
         batch = CacheBatch(kvs)
-        max_new = self.gen_kwargs["max_new_tokens"]
-        eos = self.eos_token_ids
         seen_prev = [kv._seen_tokens for kv in kvs]
-        out_ids: List[List[torch.Tensor]] = [[] for _ in range(B)]
-        cur = torch.zeros((B, 1), dtype=torch.long, device=self.device)
-        pos = torch.zeros((B, 1), dtype=torch.long, device=self.device)
-        live = [True] * B
-
-        def take(b, nxt):   # the token sequence b has just produced; retire it at EOS / the token budget
-            out_ids[b].append(nxt)
-            cur[b] = nxt[0]
-            if (eos and int(nxt) in eos) or len(out_ids[b]) >= max_new:
-                live[b] = False
-                batch.retire(b)
-
-        lens = [x.shape[1] for x in ids]
-        if self._packs_first_steps_multi(lens):
-            # first steps of all sequences in ONE forward pass: the queries back to back, every one at the positions behind its own cache
-            batch.select_packed(list(range(B)), lens)
-            p = torch.cat([torch.arange(kv.get_seq_length(), kv.get_seq_length() + n, device=self.device)
-                           for kv, n in zip(kvs, lens)]).unsqueeze(0)
-            logits = self.model(torch.cat(ids, dim=1), past_key_values=batch, use_cache=True, position_ids=p).logits
-            end = 0
-            for b, n in enumerate(lens):   # the next token of a sequence comes from its last packed position
-                end += n
-                pos[b] = kvs[b].get_seq_length()
-                take(b, self.next_token(logits[:, end - 1], self.gen_kwargs, self.sample_generator))
+        if self._packs_first_steps_multi([x.shape[1] for x in ids]):   # every query at the positions behind its own cache
+            first, pos = self._packed_first(batch, ids, [kv.get_seq_length() for kv in kvs])
         else:
+            first, pos = [], []
             for b in range(B):  # first step of every sequence: its query on its own cache, at batch 1
-                logits = self.model(ids[b], past_key_values=kvs[b], use_cache=True).logits[:, -1]
-                pos[b] = kvs[b].get_seq_length()          # (the caches have different lengths: explicit positions from here on)
-                take(b, self.next_token(logits, self.gen_kwargs, self.sample_generator))
-        while any(live):    # one token for every live sequence per step
-            logits = self.model(cur, past_key_values=batch, use_cache=True, position_ids=pos).logits[:, -1]
-            pos += 1
-            for b in range(B):
-                if live[b]:
-                    take(b, self.next_token(logits[b:b + 1], self.gen_kwargs, self.sample_generator))
-        answers = [torch.cat(o, dim=1)[:, :-1] for o in out_ids]   # (the last token is dropped: see generate)
+                first.append(self.model(ids[b], past_key_values=kvs[b], use_cache=True).logits[:, -1].clone())
+                pos.append(kvs[b].get_seq_length())       # (the caches have different lengths: explicit positions from here on)
+        answers = self._decode_slots(batch, first, pos)
         for b, kv in enumerate(kvs):
-            if not update_cache:
-                kv.slice(seen_prev[b])
-            elif kv.prefill_ids is not None:
-                kv.prefill_ids = torch.cat([kv.prefill_ids, ids[b], answers[b]], dim=1)
+            self._end_turn(kv, update_cache, seen_prev[b], ids[b], answers[b])
         return answers
 
     def head_score(self, kv) -> torch.Tensor:

@@ -147,7 +147,8 @@ def _batch(n=3, n_layers=2):
     b.n_caches, b.n_layers, b.n_heads_kv, b.n_group_kv = n, n_layers, 2, 2
     b.active = [True] * n
     b.pruned, b.get_score, b.layout = True, False, "multi"
-    b._packed = b._ptables = b._pkey = b._pws = None
+    b._packed = b._pws = None
+    b._tables = {}
     return b
 
 
@@ -214,6 +215,30 @@ def test_generate_multi_has_the_switch():
     assert m._packs_first_steps_multi([11, 3, 70]) and not m._packs_first_steps_multi([11, 0]) and not m._packs_first_steps_multi([11])
     m.multi_packed_first = False
     assert not m._packs_first_steps_multi([11, 3, 70])
+
+
+# ---- CacheBatch._table: the tables of the decode order and of a packing order (host logic only) -----------------------------------------
+def test_cache_batch_keeps_the_tables_of_both_orders(monkeypatch):
+    """A generation alternates once between a packing order and the decode order: neither evicts the other's tables, and a member's
+    layout change rebuilds both (no library call: the table is a stand-in that records what it was built from)."""
+    from kvzip_amd import kvcache
+    built = []
+    monkeypatch.setattr(kvcache.ops, "MultiTable", lambda k, v, starts, lens, slack: built.append(k) or (k, starts, lens, slack))
+    b = kvcache.CacheBatch.__new__(kvcache.CacheBatch)
+    b.caches = [types.SimpleNamespace(_layout_epoch=0, slack=8 + i, key_cache=[f"k{i}.{l}" for l in range(2)],
+                                      value_cache=[f"v{i}.{l}" for l in range(2)],
+                                      info={"meta_host": [[10 * i, 10 * i + 1, 5, 6, 0, 0]] * 2}) for i in range(3)]
+    b.n_caches, b.n_layers, b.n_heads_kv, b._tables = 3, 2, 2, {}
+    packed = b._table(1, (2, 0, 1))
+    assert packed == (["k2.1", "k0.1", "k1.1"], [[20, 21], [0, 1], [10, 11]], [[5, 6]] * 3, [10, 8, 9]) and len(built) == 2
+    decode = b._table(1)
+    assert decode[0] == ["k0.1", "k1.1", "k2.1"] and decode[3] == [8, 9, 10] and len(built) == 4
+    assert b._table(0, (2, 0, 1))[0] == ["k2.0", "k0.0", "k1.0"] and b._table(1, (2, 0, 1)) is packed and b._table(1) is decode
+    assert len(built) == 4                                               # both orders are kept: nothing was built again
+    b.caches[1]._layout_epoch = 1                                        # slack growth / tighten of one member
+    b.caches[1].key_cache = ["K1.0", "K1.1"]
+    assert b._table(1)[0] == ["k0.1", "K1.1", "k2.1"] and b._table(1, (2, 0, 1))[0] == ["k2.1", "k0.1", "K1.1"] and len(built) == 8
+    assert len(b._tables) == 2                                           # (the tables of the old layout are gone)
 
 
 # ---- the probe helpers' own expectations ---------------------------------------------------------------------------------------------
