@@ -120,6 +120,16 @@ SPEC_SIGNATURES = {
                                   _sz, _vp]),
 }
 
+# the entry points of include/kvzip_hip_retain.h (attention over the dense cache through an index of kept rows: RetainCache), bound by load()
+RETAIN_SIGNATURES = {
+    "kvz_retain_index": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "kvz_retain_index_heads": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "kvz_retain_attn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "kvz_retain_attn": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp]),
+    "kvz_retain_attn_append": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp,
+                                    _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -147,7 +157,8 @@ def load() -> C.CDLL:
         fn.argtypes = args
     for header, table in (("kvzip_hip_tighten.h", EXT_SIGNATURES), ("kvzip_hip_multi.h", MULTI_SIGNATURES),
                           ("kvzip_hip_prefill.h", PREFILL_SIGNATURES), ("kvzip_hip_multi_prefill.h", MULTI_PREFILL_SIGNATURES),
-                          ("kvzip_hip_branch.h", BRANCH_SIGNATURES), ("kvzip_hip_spec.h", SPEC_SIGNATURES)):
+                          ("kvzip_hip_branch.h", BRANCH_SIGNATURES), ("kvzip_hip_spec.h", SPEC_SIGNATURES),
+                          ("kvzip_hip_retain.h", RETAIN_SIGNATURES)):
         for name, (res, args) in table.items():
             fn = getattr(lib, name, None)
             if fn is None:   # (a library built before the header existed: same ABI version, so say what to do)

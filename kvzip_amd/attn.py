@@ -9,6 +9,7 @@ interface registry).  Hooks on the cache object, in this order (attention/attn.p
     first_step() / update_attend() of a ForkedCache                    (several queries decoding over one shared pruned cache)
     first_step() / update_attend() of a CacheBatch                     (several independent pruned caches decoding together)
     verify_attend()     the three of them for t drafted positions      (inside `with kv.verifying():`, speculative decoding)
+    update_attend() of a RetainCache                                   (pruned, indexed: attention through the index of kept rows)
 
 The dense (pre-prune) attention — flash-attn's dense kernel in the reference (attention/attn.py:75-89) — runs on the
 library's multi-row kernel (``ops.flash_fwd`` -> ``kvz_flash_fwd``), registered as the attention implementation
@@ -107,6 +108,11 @@ def llama_qwen_attn_forward(self, hidden_states: torch.Tensor,
             and not getattr(kv, "get_score", None) and getattr(kv, "layout", None) == "slack"
             and q_len * (query_states.shape[1] // key_states.shape[1]) <= 64):
         return _rows_out(self, kv.verify_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling), bsz, q_len)
+    # pruned non-evicting cache (kvcache.RetainCache, indexed): the new rows go into the dense store and the queries attend to the kept
+    # rows through the index of kept positions - no plan, gather or host round trip per call (bit-identical to the generic route below)
+    if (getattr(kv, "indexed", False) and getattr(kv, "pruned", None) and not getattr(kv, "get_score", None)
+            and kv.index_takes(query_states)):
+        return _rows_out(self, kv.update_attend(query_states, key_states, value_states, self.layer_idx, softmax_scale=self.scaling), bsz, q_len)
     if kv is not None:
         key_states, value_states = kv.update(key_states, value_states, self.layer_idx)
 

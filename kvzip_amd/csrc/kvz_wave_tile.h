@@ -1,5 +1,5 @@
 // kvz_wave_tile.h - what the split-K attention kernels (kvz_attn.hip, kvz_fork.hip, kvz_multi.hip, kvz_fork_prefill.hip,
-// kvz_multi_prefill.hip, kvz_spec.hip) share: the vector types, the MFMA traits, the constants of the wave tile and the host-side cut into work items.
+// kvz_multi_prefill.hip, kvz_spec.hip, kvz_retain.hip) share: the vector types, the MFMA traits, the constants of the wave tile and the host-side cut into work items.
 //
 // Tile scheme.  A WAVE owns a tile of 32 keys (KT) x 16 query rows (RT):
 //   S^T = K.Q^T   on v_mfma_f32_16x16x32 with the K rows loaded straight from memory as the A operand (16 contiguous bytes per lane,

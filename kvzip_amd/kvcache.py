@@ -88,18 +88,7 @@ class _CacheBase(KVScore):
             self.key_cache.append(None)
             self.value_cache.append(None)
         f = self._fill[layer_idx]
-        sk, sv = self._store_k[layer_idx], self._store_v[layer_idx]
-        cap = sk.shape[2]
-        if f + t > cap:  # amortised growth
-            self._wait_score(finalize=False)  # (scoring calls in flight read the storage that is being replaced)
-            new_cap = max(2 * cap, f + t + self._reserve)
-            for store in (self._store_k, self._store_v):
-                old = store[layer_idx]
-                new = torch.empty((1, old.shape[1], new_cap, old.shape[3]), dtype=old.dtype, device=old.device)
-                new[:, :, :f].copy_(old[:, :, :f])
-                store[layer_idx] = new
-            sk, sv = self._store_k[layer_idx], self._store_v[layer_idx]
-            self._views.clear()
+        sk, sv = self._dense_grow(layer_idx, f + t)
         fast = key_states.is_cuda and key_states.stride(-1) == 1 and value_states.stride(-1) == 1
         if fast and self.get_score and not self.pruned and self.fuse_update_score and self.score_deferred:
             # scoring pass: _get_score of this layer follows (attention/attn.py:44-54) and issues the append together with the
@@ -120,11 +109,33 @@ class _CacheBase(KVScore):
                 self._wait_score(layer_idx)
             sk[:, :, f:f + t].copy_(key_states)
             sv[:, :, f:f + t].copy_(value_states)
-        self._fill[layer_idx] = f + t
+        self._dense_commit(layer_idx, f + t)
+
+    def _dense_grow(self, layer_idx: int, need: int):
+        """The layer's stores with room for ``need`` rows per head (amortised growth: the filled rows move to a larger buffer)."""
+        f = self._fill[layer_idx]
+        sk, sv = self._store_k[layer_idx], self._store_v[layer_idx]
+        cap = sk.shape[2]
+        if need > cap:
+            self._wait_score(finalize=False)  # (scoring calls in flight read the storage that is being replaced)
+            new_cap = max(2 * cap, need + self._reserve)
+            for store in (self._store_k, self._store_v):
+                old = store[layer_idx]
+                new = torch.empty((1, old.shape[1], new_cap, old.shape[3]), dtype=old.dtype, device=old.device)
+                new[:, :, :f].copy_(old[:, :, :f])
+                store[layer_idx] = new
+            sk, sv = self._store_k[layer_idx], self._store_v[layer_idx]
+            self._views.clear()
+        return sk, sv
+
+    def _dense_commit(self, layer_idx: int, rows: int):
+        """``rows`` rows per head of the layer are in use: the fill count and the ``key_cache`` / ``value_cache`` views."""
+        sk, sv = self._store_k[layer_idx], self._store_v[layer_idx]
+        self._fill[layer_idx] = rows
         # views of the filled part: the same lengths come back chunk after chunk (update ... slice), so they are cached
-        vw = self._views.get((layer_idx, f + t))
+        vw = self._views.get((layer_idx, rows))
         if vw is None or vw[2] is not sk:
-            vw = self._views[(layer_idx, f + t)] = (sk[:, :, :f + t], sv[:, :, :f + t], sk)
+            vw = self._views[(layer_idx, rows)] = (sk[:, :, :rows], sv[:, :, :rows], sk)
             if len(self._views) > 16 * max(1, self.n_layers):
                 self._views.clear()
         self.key_cache[layer_idx], self.value_cache[layer_idx] = vw[0], vw[1]
@@ -1173,10 +1184,15 @@ class RetainCache(_CacheBase):
     Produces the same flattened tensors as :class:`EvictCache` (the reference's internal cross-check)."""
 
     def __init__(self, model, evict_range: Tuple[int, int], device=None, dtype=None, reserve: int = 4096,
-                 verbose: bool = True):
+                 verbose: bool = True, indexed: bool = True):
         super().__init__(model, evict_range, device=device, dtype=dtype, reserve=reserve)
         self.verbose = verbose
         self._cu_head = torch.arange(self.n_heads_kv + 1, dtype=torch.int32, device=self.device)
+        # indexed: ``prune`` turns the mask into an index of kept positions (ops.RetainIndex) and decode steps attend through it over
+        # the dense store (``update_attend``: no plan, no gather, no host round trip per call); False: every call takes ``prepare``
+        self.indexed = bool(indexed)
+        self._index: Optional["ops.RetainIndex"] = None
+        self._index_valid = None                 # the mask the index was built from (a replaced ``valid`` drops the index)
 
     # reference: kvcache.py:244-267
     def update(self, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int, cache_kwargs=dict()):
@@ -1200,11 +1216,66 @@ class RetainCache(_CacheBase):
     # reference: kvcache.py:284-298
     def prune(self, ratio: float, level: str = "pair"):
         """Prune the KV cache (fake): only the mask is computed; it is applied before every attention."""
+        self._index = self._index_valid = None
         thres, r_ = self._select(ratio, level)
         self.pruned = True
+        if self.indexed:
+            self._build_index()
         if self.verbose:
             print(f"ratio {r_:.2f} ({level}), threshold {thres:.4f} (evict {self._evicted:.0f} pairs)")
         return thres, r_
+
+    def _build_index(self):
+        """Kept positions of every (layer, head) under the current mask: the plan at ``klen = sink + N``, ONE copy of the per-head
+        counts to the host, one launch for all layers.  It holds positions, not addresses: growing the dense store leaves it valid."""
+        if not self.valid.is_cuda or self.n_heads_kv > 64:   # (the kernel's limit; such a cache keeps the gather route)
+            return
+        plan = ops.compact_plan(self.valid, self.sink, self.sink + self.ctx_len, slack=0)
+        self._index = ops.retain_index(plan)
+        self._index_valid = self.valid
+
+    def adopt_dense(self, store_k: List[torch.Tensor], store_v: List[torch.Tensor], filled: int):
+        self._index = self._index_valid = None
+        super().adopt_dense(store_k, store_v, filled)
+
+    def index_takes(self, query_states: torch.Tensor) -> bool:
+        """True when a forward pass with these queries attends through the index: the cache is pruned under the mask the index
+        was built from and the kernel takes the shape (batch 1, fp16 / bf16, head dim 64 / 128, few enough query rows per KV head;
+        more rows - a long first step - gather and run the multi-row kernel, ``prepare`` + ``attend``)."""
+        if not (self.indexed and self.pruned and self._index is not None and self._index_valid is self.valid):
+            return False
+        bsz, _, q_len, dim = query_states.shape
+        if bsz != 1 or not query_states.is_cuda or query_states.dtype not in (torch.float16, torch.bfloat16):
+            return False
+        return ops._lib.load().kvz_retain_attn_workspace_bytes(self.n_heads_kv, self.n_group_kv, q_len, dim) > 0 and dim in (64, 128)
+
+    def update_attend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
+                      softmax_scale: Optional[float] = None) -> torch.Tensor:
+        """``update`` + ``prepare`` + ``attend`` through the index (``index_takes`` said so): the new rows go into the dense store and
+        the queries attend to the kept rows where they lie.  A decode step (one token) is ONE library call that also writes the
+        token's row; a few positions are ``update`` followed by one call.  ``_fill``, the ``key_cache`` / ``value_cache`` views and
+        ``_seen_tokens`` end up exactly as after ``update``.  Returns ``[Hkv*q_len, G, D]`` like ``attend``: the bits of the gather
+        route."""
+        bsz, _, q_len, dim = query_states.shape
+        ix = self._index
+        ws = self._attn_workspace(q_len, dim, query_states.device)
+        if q_len == 1 and key_states.stride(-1) == 1 and value_states.stride(-1) == 1:
+            if layer_idx == 0:
+                self._seen_tokens += 1
+            self._flush_append()
+            if self._pending:
+                self._wait_score(layer_idx)
+            f = self._fill[layer_idx]
+            sk, sv = self._dense_grow(layer_idx, f + 1)
+            out = ops.retain_attn_append(query_states.reshape(-1, self.n_group_kv, dim), sk, sv, key_states, value_states, ix.idx,
+                                         ix.meta_host[layer_idx], ix.ctx_end, f, softmax_scale=softmax_scale, workspace=ws)
+            self._dense_commit(layer_idx, f + 1)
+            return out
+        self.update(key_states, value_states, layer_idx)
+        query_states = query_states.view(bsz, self.n_heads_kv, self.n_group_kv, q_len, dim)
+        query_states = query_states.transpose(2, 3).contiguous().view(-1, self.n_group_kv, dim)
+        return ops.retain_attn(query_states, self._store_k[layer_idx], self._store_v[layer_idx], ix.idx, ix.meta_host[layer_idx],
+                               ix.ctx_end, self._fill[layer_idx], q_len, causal=True, softmax_scale=softmax_scale, workspace=ws)
 
     # reference: kvcache.py:312-347
     def prepare(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,

@@ -622,6 +622,114 @@ def spec_attn_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     return out
 
 
+# --------------------------------------------------------------------------------------------------
+# attention over the dense cache through an index of kept rows (include/kvzip_hip_retain.h): RetainCache
+# --------------------------------------------------------------------------------------------------
+class RetainIndex:
+    """Kept positions of every (layer, head) of a mask, packed back to back (``kvz_retain_index``), and what the host knows of them.
+    ``idx`` int32 ``[max(total, 1)]`` on the device; ``starts[l][h]`` / ``counts[l][h]`` python ints; ``meta_host[l]`` the ctypes array
+    ``starts ++ counts`` of layer l that the attention calls pass on by value; ``ctx_end`` = sink + N."""
+
+    def __init__(self, idx: torch.Tensor, row_start: torch.Tensor, starts, counts, ctx_end: int):
+        import ctypes as C
+        self.idx, self.row_start, self.starts, self.counts, self.ctx_end = idx, row_start, starts, counts, int(ctx_end)
+        self.total = sum(sum(c) for c in counts)
+        Hkv = len(counts[0])
+        self.meta_host = [(C.c_int32 * (2 * Hkv))(*s, *c) for s, c in zip(starts, counts)]
+
+
+def retain_index(plan: CompactPlan, counts_host=None) -> RetainIndex:
+    """Index of the positions in ``[0, sink + N)`` that the full mask of ``plan`` keeps (``compact_plan(valid, sink, sink + N)``: lengths
+    and tile bases are the plan's).  One launch for all layers; ``counts_host`` (``[L][Hkv]``) spares the one copy of the lengths to the
+    host when the caller has them already."""
+    lib = _lib.load()
+    assert plan.klen == plan.sink + plan.N, "the index covers the context: plan with klen = sink + N"
+    L, Hkv = plan.layers, plan.Hkv
+    counts = counts_host if counts_host is not None else plan.len_k.cpu().tolist()   # (one D2H copy per prune)
+    starts, o = [], 0
+    for l in range(L):
+        row = []
+        for h in range(Hkv):
+            row.append(o)
+            o += int(counts[l][h])
+        starts.append(row)
+    if o >= 2 ** 31:
+        raise KvzError(f"retain index: {o} kept rows over all layers do not fit 32-bit entries")
+    dev = plan.tile_base.device
+    row_start = torch.tensor(starts, dtype=torch.int32).to(dev)
+    idx = torch.empty(max(o, 1), dtype=torch.int32, device=dev)
+    heads = getattr(plan, "heads", False)
+    fn = lib.kvz_retain_index_heads if heads else lib.kvz_retain_index
+    rc = fn(plan.valid.data_ptr(), L, Hkv, plan.N, plan.sink, plan.tile_base.data_ptr(), row_start.data_ptr(), idx.data_ptr(), o,
+            _stream(idx))
+    check(rc, "kvz_retain_index_heads" if heads else "kvz_retain_index")
+    return RetainIndex(idx, row_start, starts, [[int(c) for c in r] for r in counts], plan.klen)
+
+
+def retain_attn_workspace(Hkv: int, G: int, q_len: int, D: int, device) -> torch.Tensor:
+    """Scratch of ``retain_attn`` / ``retain_attn_append`` (partials of the key ranges); no initialisation needed."""
+    need = _lib.load().kvz_retain_attn_workspace_bytes(Hkv, G, q_len, D)
+    return torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+
+
+def _retain_store(k_store: torch.Tensor, v_store: torch.Tensor):
+    """(Hkv, capacity, D, head stride) of a dense ``[1, Hkv, capacity, D]`` (or ``[Hkv, capacity, D]``) store pair."""
+    Hkv, cap, D = k_store.shape[-3:]
+    assert v_store.shape == k_store.shape and v_store.dtype == k_store.dtype
+    assert k_store.stride(-1) == 1 and k_store.stride(-2) == D and v_store.stride()[-3:] == k_store.stride()[-3:]
+    return Hkv, cap, D, k_store.stride(-3)
+
+
+def retain_attn(q: torch.Tensor, k_store: torch.Tensor, v_store: torch.Tensor, idx: torch.Tensor, meta_host, ctx_end: int, fill: int,
+                q_len: int, causal: bool = True, softmax_scale: Optional[float] = None, workspace: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q ``[Hkv*q_len, G, D]`` (row p*G + g of head h, as ``prepare`` lays them out) over the dense store ``[1, Hkv, capacity, D]`` of
+    which ``fill`` rows per head are in use: head h attends to the positions ``idx[start_h : start_h + n_h]`` (``meta_host`` = ctypes
+    int32 ``starts ++ counts``) and to the rows ``ctx_end .. fill - 1``.  Returns ``[Hkv*q_len, G, D]``: the bits of ``varlen_attn`` on
+    the compacted copy of the same rows."""
+    lib = _lib.load()
+    HQ, G, D = q.shape
+    Hkv, cap, Ds, hs = _retain_store(k_store, v_store)
+    assert Hkv * q_len == HQ and Ds == D and q.is_contiguous() and idx.dtype == torch.int32 and idx.is_contiguous()
+    _same_device(q, k_store, v_store, idx, workspace, out)
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty_like(q)
+    if workspace is None:
+        workspace = retain_attn_workspace(Hkv, G, q_len, D, q.device)
+    rc = lib.kvz_retain_attn(q.data_ptr(), k_store.data_ptr(), v_store.data_ptr(), hs, cap, idx.data_ptr(), idx.numel(), meta_host,
+                             int(ctx_end), int(fill), Hkv, G, q_len, D, float(scale), 1 if causal else 0, _dtype_code(q.dtype),
+                             out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(q))
+    check(rc, "kvz_retain_attn")
+    return out
+
+
+def retain_attn_append(q: torch.Tensor, k_store: torch.Tensor, v_store: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
+                       idx: torch.Tensor, meta_host, ctx_end: int, fill: int, softmax_scale: Optional[float] = None,
+                       workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Decode step in one call: write the new token's K, V (``[1, Hkv, 1, D]``, any head stride) into row ``fill`` of every head of
+    the dense store and attend q (``[Hkv, G, D]``) over the indexed positions and the rows ``ctx_end .. fill``.  Bit-identical to
+    ``kvz_dense_append`` followed by ``retain_attn`` with ``fill + 1``."""
+    lib = _lib.load()
+    Hkv, G, D = q.shape
+    Hs, cap, Ds, hs = _retain_store(k_store, v_store)
+    assert Hs == Hkv and Ds == D and q.is_contiguous() and idx.dtype == torch.int32 and idx.is_contiguous()
+    assert k_new.shape[-3] == Hkv and k_new.shape[-2] == 1 and v_new.shape[-2] == 1 and k_new.shape[-1] == D
+    assert k_new.stride(-1) == 1 and v_new.stride(-1) == 1
+    _same_device(q, k_store, v_store, k_new, v_new, idx, workspace, out)
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty_like(q)
+    if workspace is None:
+        workspace = retain_attn_workspace(Hkv, G, 1, D, q.device)
+    rc = lib.kvz_retain_attn_append(q.data_ptr(), k_store.data_ptr(), v_store.data_ptr(), hs, cap, k_new.data_ptr(), v_new.data_ptr(),
+                                    k_new.stride(-3), v_new.stride(-3), idx.data_ptr(), idx.numel(), meta_host, int(ctx_end), int(fill),
+                                    Hkv, G, D, float(scale), _dtype_code(q.dtype), out.data_ptr(), workspace.data_ptr(),
+                                    workspace.numel(), _stream(q))
+    check(rc, "kvz_retain_attn_append")
+    return out
+
+
 def fork_prefill_tail(query: torch.Tensor, cu_q: Sequence[int], tail_k: torch.Tensor, tail_v: torch.Tensor, tail_len: Sequence[int],
                       k_new: torch.Tensor, v_new: torch.Tensor, o_shared: torch.Tensor, lse_shared: torch.Tensor,
                       softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
