@@ -130,6 +130,15 @@ RETAIN_SIGNATURES = {
                                     _sz, _vp]),
 }
 
+# the entry points of include/kvzip_hip_tree.h (tree speculative decoding: verify a tree of drafted nodes, keep the accepted path), bound
+# by load()
+TREE_SIGNATURES = {
+    "kvz_tree_attn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "kvz_tree_attn_append": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _f, _i, _vp, _vp,
+                                  _sz, _vp, _vp]),
+    "kvz_tree_keep_path": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -158,7 +167,7 @@ def load() -> C.CDLL:
     for header, table in (("kvzip_hip_tighten.h", EXT_SIGNATURES), ("kvzip_hip_multi.h", MULTI_SIGNATURES),
                           ("kvzip_hip_prefill.h", PREFILL_SIGNATURES), ("kvzip_hip_multi_prefill.h", MULTI_PREFILL_SIGNATURES),
                           ("kvzip_hip_branch.h", BRANCH_SIGNATURES), ("kvzip_hip_spec.h", SPEC_SIGNATURES),
-                          ("kvzip_hip_retain.h", RETAIN_SIGNATURES)):
+                          ("kvzip_hip_retain.h", RETAIN_SIGNATURES), ("kvzip_hip_tree.h", TREE_SIGNATURES)):
         for name, (res, args) in table.items():
             fn = getattr(lib, name, None)
             if fn is None:   # (a library built before the header existed: same ABI version, so say what to do)

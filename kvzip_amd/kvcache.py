@@ -560,14 +560,20 @@ class EvictCache(_CacheBase):
 
     # ---- speculative decoding: verify t drafted positions in one step, take the rejected ones back ------------------------------
     @contextlib.contextmanager
-    def verifying(self):
+    def verifying(self, tree=None):
         """While inside, a forward pass of 2 .. 64 // G tokens on this pruned slack-layout cache takes ``verify_attend``
-        (kvzip_amd.attn).  Only the speculative loop sets it: without it every forward goes where it always went."""
+        (kvzip_amd.attn).  Only the speculative loop sets it: without it every forward goes where it always went.  ``tree=parents``
+        (``parents[0] = -1``, ``parents[i] < i``): the ``len(parents)`` tokens of such a forward are the nodes of a tree, node i
+        continuing node ``parents[i]``, and ``verify_attend`` masks the new rows by ancestry (``kvz_tree_attn_append``);
+        ``keep_path`` afterwards keeps the rows of the accepted path."""
+        # (raises for what is no tree before anything is set; converted once for the calls of all layers)
+        anc = ops.mask_array(ops.ancestor_masks(tree)) if tree is not None else None
         prev, self._verifying = getattr(self, "_verifying", False), True
+        prev_anc, self._verify_anc = getattr(self, "_verify_anc", None), anc
         try:
             yield self
         finally:
-            self._verifying = prev
+            self._verifying, self._verify_anc = prev, prev_anc
 
     def verify_attend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor, layer_idx: int,
                       softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -575,10 +581,14 @@ class EvictCache(_CacheBase):
         ``q_len = t`` in one call of ``kvz_spec_attn_append``, which reads the kept rows once (twice beyond 32 query rows per KV
         head) and writes the t K,V rows into the slack of every head.  query ``[1, H, t, D]``, key / value ``[1, Hkv, t, D]``;
         returns ``[Hkv*t, G, D]`` like ``attend``.  The cache bookkeeping (``_seen_tokens``, ``info["offset"]``) ends up exactly as
-        after the three separate calls; ``rewind`` takes positions back."""
+        after the three separate calls; ``rewind`` takes positions back.  Inside ``verifying(tree=parents)`` the t positions are the
+        nodes of that tree and the call is ``kvz_tree_attn_append``: same rows written, node p attends to its ancestors among them."""
         assert self.info["flatten"] and self.layout == "slack" and query_states.shape[0] == 1
         t, dim = query_states.shape[-2], query_states.shape[-1]
         Hkv, G = self.n_heads_kv, self.n_group_kv
+        anc = getattr(self, "_verify_anc", None)
+        if anc is not None and len(anc) != t:
+            raise ops.KvzError(f"verify_attend: a forward pass of {t} tokens inside verifying(tree=...) of {len(anc)} nodes")
         if layer_idx == 0:
             self._seen_tokens += t
         off = self.info["offset"][layer_idx]
@@ -588,9 +598,14 @@ class EvictCache(_CacheBase):
         ws = self._spec_workspace(t, dim, query_states.device)
         if out is not None:
             out = out.view(Hkv, t, G, dim)
-        out = ops.spec_attn_append(q, self.key_cache[layer_idx], self.value_cache[layer_idx], self.info["seg_start"][layer_idx],
-                                   self.info["len_k"][layer_idx], off, self.slack, key_states[0], value_states[0],
-                                   softmax_scale=softmax_scale, workspace=ws, meta_host=self._meta_host(layer_idx), out=out)
+        if anc is not None:
+            out = ops.tree_attn_append(q, self.key_cache[layer_idx], self.value_cache[layer_idx], self.info["seg_start"][layer_idx],
+                                       self.info["len_k"][layer_idx], off, self.slack, key_states[0], value_states[0], anc,
+                                       softmax_scale=softmax_scale, workspace=ws, meta_host=self._meta_host(layer_idx), out=out)
+        else:
+            out = ops.spec_attn_append(q, self.key_cache[layer_idx], self.value_cache[layer_idx], self.info["seg_start"][layer_idx],
+                                       self.info["len_k"][layer_idx], off, self.slack, key_states[0], value_states[0],
+                                       softmax_scale=softmax_scale, workspace=ws, meta_host=self._meta_host(layer_idx), out=out)
         self.info["offset"][layer_idx] = off + t
         return out.view(Hkv * t, G, dim)
 
@@ -614,6 +629,36 @@ class EvictCache(_CacheBase):
             raise ops.KvzError(f"rewind: {n} positions, but {have} were appended since the prune or the last slice")
         self.info["offset"] = [o - n for o in self.info["offset"]]
         self._seen_tokens -= n
+
+    def keep_path(self, path, t: int) -> None:
+        """After a tree verify step of ``t`` nodes (``verifying(tree=...)``): keep the rows of the accepted path - ``path`` ascending
+        node indices, ``path[i] >= i`` - in the first ``len(path)`` of the t slots behind every head segment, in every layer (one
+        ``kvz_tree_keep_path`` launch for all layers, none for an identity path), and take the other ``t - len(path)`` positions back
+        (``rewind``).  Called between forward passes.  ``KvzError`` before anything is touched for a cache that is not a pruned
+        slack-layout one, offsets that differ between layers or are below ``t``, or a bad path."""
+        t = int(t)
+        path = [int(x) for x in path]
+        if not (self.info.get("flatten") and self.layout == "slack"):
+            raise ops.KvzError("keep_path: only a pruned slack-layout cache holds the node rows of a tree verify step behind its segments")
+        offs = self.info["offset"]
+        if min(offs) != max(offs):
+            raise ops.KvzError(f"keep_path: the layers hold different numbers of appended positions ({min(offs)} .. {max(offs)}): call it "
+                               "between forward passes")
+        if not 1 <= t <= ops.TREE_MAX_NODES or offs[0] < t:
+            raise ops.KvzError(f"keep_path: t = {t} node rows, but {offs[0]} positions were appended since the prune or the last slice "
+                               f"(1 .. {ops.TREE_MAX_NODES} nodes)")
+        for i, x in enumerate(path):
+            if x < i or x >= t or (i and x <= path[i - 1]):
+                raise ops.KvzError(f"keep_path: path[{i}] = {x}: a path is strictly ascending with i <= path[i] < t = {t}")
+        if any(x != i for i, x in enumerate(path)):
+            Hkv, base = self.n_heads_kv, offs[0] - t
+            row0 = []
+            for l in range(self.n_layers):
+                mh = self._meta_host(l)
+                starts = list(mh[:Hkv]) if mh is not None else self.info["seg_start"][l].tolist()
+                row0 += [starts[h] + self.info["len_k_host"][l][h] + base for h in range(Hkv)]
+            ops.tree_keep_path(self.key_cache, self.value_cache, row0, path, t)
+        self.rewind(t - len(path))
 
     def fork(self, n_branches: int, tail_capacity: int = 256) -> "ForkedCache":
         """``n_branches`` concurrent queries over this pruned cache: the branches share its rows read-only and each owns a private

@@ -623,6 +623,97 @@ def spec_attn_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
 
 
 # --------------------------------------------------------------------------------------------------
+# tree speculative decoding (include/kvzip_hip_tree.h): verify a tree of drafted nodes in one step, keep the accepted path
+# --------------------------------------------------------------------------------------------------
+TREE_MAX_NODES = 64     # nodes of one verify step: one bit each in an ancestor mask
+
+
+def ancestor_masks(parents: Sequence[int]) -> list:
+    """Ancestor masks of a tree given by its parent vector (``parents[0] = -1``, ``parents[i] < i``: topological order): entry p has
+    bit j set iff node j is p itself or one of its ancestors.  Pure Python; at most ``TREE_MAX_NODES`` nodes."""
+    parents = [int(x) for x in parents]
+    t = len(parents)
+    if t == 0:
+        return []
+    if t > TREE_MAX_NODES:
+        raise KvzError(f"ancestor_masks: {t} nodes (at most {TREE_MAX_NODES}: one bit each)")
+    if parents[0] != -1:
+        raise KvzError(f"ancestor_masks: parents[0] = {parents[0]} (node 0 is the root: -1)")
+    masks = [1]
+    for i in range(1, t):
+        if not 0 <= parents[i] < i:
+            raise KvzError(f"ancestor_masks: parents[{i}] = {parents[i]} (a node continues an EARLIER node: 0 .. {i - 1})")
+        masks.append(masks[parents[i]] | (1 << i))
+    return masks
+
+
+def mask_array(anc: Sequence[int]):
+    """The ancestor masks as the ctypes uint64 array ``tree_attn_append`` hands to the library."""
+    import ctypes as C
+    return (C.c_uint64 * len(anc))(*[int(m) for m in anc])
+
+
+def tree_attn_workspace(t: int, Hkv: int, G: int, D: int, device) -> torch.Tensor:
+    """Scratch of ``tree_attn_append`` (the size of the chain verify call's); no initialisation needed."""
+    need = _lib.load().kvz_tree_attn_workspace_bytes(t, Hkv, G, D)
+    return torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+
+
+def tree_attn_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_start: Optional[torch.Tensor],
+                     k_len: Optional[torch.Tensor], k_len_offset: int, slack: int, k_new: torch.Tensor, v_new: torch.Tensor,
+                     anc: Sequence[int], softmax_scale: Optional[float] = None, workspace: Optional[torch.Tensor] = None,
+                     meta_host=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One verify step over a TREE of t nodes on a pruned slack-layout cache (``kvz_tree_attn_append``).  Shapes as
+    ``spec_attn_append``; ``anc`` are the t ancestor masks (``ancestor_masks``, or ``mask_array`` of them).  Appends the t rows behind every segment in node
+    order and returns ``[Hkv, t, G, D]``: node p attends to the old rows and to the new rows whose bit is set in ``anc[p]``."""
+    import ctypes as C
+    lib = _lib.load()
+    Hkv, t, G, D = q.shape
+    assert q.is_contiguous() and k_cache.is_contiguous() and v_cache.is_contiguous()
+    assert k_new.shape == (Hkv, t, D) and v_new.shape == (Hkv, t, D) and k_new.stride(-1) == 1 and v_new.stride(-1) == 1
+    assert (k_start is None) == (k_len is None) and (k_start is not None or meta_host is not None)
+    assert k_start is None or (k_start.dtype == torch.int32 and k_len.dtype == torch.int32)
+    assert len(anc) == t
+    _same_device(q, k_cache, v_cache, k_new, v_new, workspace, out)
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty_like(q)
+    assert out.shape == q.shape and out.is_contiguous() and out.dtype == q.dtype
+    if workspace is None:
+        workspace = tree_attn_workspace(t, Hkv, G, D, q.device)
+    masks = anc if isinstance(anc, C.Array) else mask_array(anc)     # (a caller with one tree for all layers converts once)
+    rc = lib.kvz_tree_attn_append(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(k_start), _ptr(k_len), int(k_len_offset),
+                                  meta_host, int(slack), k_new.data_ptr(), v_new.data_ptr(), k_new.stride(0), k_new.stride(1),
+                                  v_new.stride(0), v_new.stride(1), t, Hkv, G, D, float(scale), _dtype_code(q.dtype), out.data_ptr(),
+                                  workspace.data_ptr(), workspace.numel(), masks, _stream(q))
+    check(rc, "kvz_tree_attn_append")
+    return out
+
+
+def tree_keep_path(k_caches: Sequence[torch.Tensor], v_caches: Sequence[torch.Tensor], row0: Sequence[int], path: Sequence[int],
+                   t: int) -> None:
+    """Keep the accepted path of the t node rows a tree verify step appended (``kvz_tree_keep_path``), all layers in one launch:
+    k_caches / v_caches are the flat ``[rows, D]`` caches of the layers, ``row0[l * Hkv + h]`` the row of node 0's slot of (layer,
+    head); row ``path[i]`` of every slot run ends up at slot i, in place.  An identity path launches nothing."""
+    import ctypes as C
+    lib = _lib.load()
+    L = len(k_caches)
+    assert L > 0 and len(v_caches) == L and len(row0) % L == 0
+    Hkv = len(row0) // L
+    D, dtype = k_caches[0].shape[-1], k_caches[0].dtype
+    for k, v in zip(k_caches, v_caches):
+        assert k.is_contiguous() and v.is_contiguous() and k.shape[-1] == D and v.shape[-1] == D and k.dtype == dtype and v.dtype == dtype
+    _same_device(*k_caches, *v_caches)
+    kp = (C.c_void_p * L)(*[k.data_ptr() for k in k_caches])
+    vp = (C.c_void_p * L)(*[v.data_ptr() for v in v_caches])
+    r0 = (C.c_int32 * len(row0))(*[int(x) for x in row0])
+    n = len(path)
+    ph = (C.c_int32 * max(n, 1))(*[int(x) for x in path])
+    rc = lib.kvz_tree_keep_path(L, kp, vp, r0, ph, n, int(t), Hkv, D, _dtype_code(dtype), _stream(k_caches[0]))
+    check(rc, "kvz_tree_keep_path")
+
+
+# --------------------------------------------------------------------------------------------------
 # attention over the dense cache through an index of kept rows (include/kvzip_hip_retain.h): RetainCache
 # --------------------------------------------------------------------------------------------------
 class RetainIndex:

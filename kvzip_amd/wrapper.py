@@ -350,7 +350,7 @@ class ModelKVzip:
     @_on_model_device
     @torch.inference_mode()
     def generate_speculative(self, query: Union[str, torch.Tensor], kv, draft=None, num_draft: Optional[int] = None,
-                             update_cache: bool = False, return_ids: bool = False, return_stats: bool = False):
+                             update_cache: bool = False, return_ids: bool = False, return_stats: bool = False, tree: bool = False):
         """``generate`` by draft-and-verify on a pruned slack-layout cache, greedy (no reference counterpart).  After the query's
         first step every further step asks the drafter for up to ``num_draft`` ids (``draft(history_ids, n)`` if given, else prompt
         lookup over ``kv.prefill_ids ++ query ++ answer``, ``draft.lookup_draft``), runs ``[last token] ++ draft`` through the model
@@ -359,8 +359,16 @@ class ModelKVzip:
         empty draft is a plain decode step.  Same tokens as ``generate`` up to the summation order of the attention (an argmax may
         tie); the answer ends at the first EOS or at ``max_new_tokens``, its last token is dropped and the cache is left as
         ``generate`` leaves it.  ``return_stats``: also ``{"steps", "tokens", "drafted", "accepted"}`` (forward passes after the query's,
-        tokens they produced, ids drafted, ids accepted).  End-to-end gain depends on the drafter's hit rate."""
-        from .draft import accept_greedy, lookup_draft
+        tokens they produced, ids drafted, ids accepted).  End-to-end gain depends on the drafter's hit rate.
+
+        ``tree=True``: a step verifies a TREE of candidates, so that several continuations share the forward pass.  The drafter is
+        ``draft(history_ids, n) -> (ids, parents)`` (default ``draft.lookup_tree``): up to n nodes behind the root, the last token;
+        ``parents[i]`` is the node ``ids[i]`` (node i + 1) continues, 0 being the root, parents before children.  Node i runs at
+        position ``seen + depth(i)`` and attends to its ancestors among the new rows (``kv.verifying(tree=...)``);
+        ``draft.accept_tree_greedy`` picks the path the model agrees with, ``kv.keep_path`` keeps its rows.  The node budget is
+        ``num_draft``'s (t*G <= 32 query rows per KV head by default, at most 64).  Stats also carry ``"nodes"``, the positions the
+        verify steps ran (root included); ``"drafted"`` counts the nodes behind the roots, ``"accepted"`` those on accepted paths."""
+        from .draft import accept_greedy, accept_tree_greedy, lookup_draft, lookup_tree
         if self.gen_kwargs.get("do_sample", False):
             raise ValueError("generate_speculative is greedy: do_sample=True needs a distribution-preserving acceptance rule, use generate")
         if not (isinstance(kv, EvictCache) and pruned_slack(kv)):
@@ -371,10 +379,12 @@ class ModelKVzip:
         max_new = self.gen_kwargs["max_new_tokens"]
         eos = self.eos_token_ids
         n_draft = self._draft_len(num_draft)
-        drafter = draft if draft is not None else lookup_draft
+        drafter = draft if draft is not None else (lookup_tree if tree else lookup_draft)
         prior = [kv.prefill_ids[0]] if getattr(kv, "prefill_ids", None) is not None else []
         history = torch.cat(prior + [input_ids[0]])
         stats = {"steps": 0, "tokens": 0, "drafted": 0, "accepted": 0}
+        if tree:
+            stats["nodes"] = 0
         logits = self.model(input_ids, past_key_values=kv, use_cache=True).logits[:, -1]
         out = [int(logits.argmax(-1))]          # invariant: the cache holds the query and out[:-1]
         while len(out) < max_new and out[-1] not in eos:
@@ -382,7 +392,11 @@ class ModelKVzip:
             last = torch.tensor([out[-1]], dtype=torch.long, device=self.device)
             history = torch.cat([history, last])
             d_ids = history[:0]
-            if n_draft > 0 and room > 1:
+            if n_draft > 0 and room > 1 and tree:
+                d_ids, parents = drafter(history, min(n_draft, room - 1))
+                d_ids = torch.as_tensor(d_ids, dtype=torch.long).reshape(-1)[:min(n_draft, room - 1)].to(self.device)
+                parents = [int(x) for x in parents][:int(d_ids.shape[0])]     # (parents precede children: a prefix is a tree)
+            elif n_draft > 0 and room > 1:
                 d_ids = drafter(history, min(n_draft, room - 1)).reshape(-1)[:min(n_draft, room - 1)].to(self.device)
             d = int(d_ids.shape[0])
             stats["steps"] += 1
@@ -392,6 +406,28 @@ class ModelKVzip:
                 stats["tokens"] += 1
                 continue
             cur = torch.cat([last, d_ids])[None]
+            if tree:
+                depth = [0]
+                for par in parents:             # (node i + 1 continues node parents[i]; ancestor_masks checks the order)
+                    depth.append(depth[par] + 1 if 0 <= par < len(depth) else 0)
+                pos = (kv._seen_tokens + torch.tensor(depth, device=self.device))[None]
+                with kv.verifying(tree=[-1] + parents):
+                    argmax = self.model(cur, past_key_values=kv, use_cache=True, position_ids=pos).logits[0].argmax(-1)
+                argmax = argmax.tolist()
+                path = accept_tree_greedy(d_ids, parents, argmax)
+                ids_l = d_ids.tolist()
+                new = [ids_l[i - 1] for i in path[1:]] + [argmax[path[-1]]]
+                stats["accepted"] += len(path) - 1
+                stats["nodes"] += d + 1
+                for j, tok in enumerate(new):   # an EOS on the path ends the answer there: the nodes behind it are not kept
+                    if tok in eos:
+                        path, new = path[:j + 1], new[:j + 1]
+                        break
+                kv.keep_path(path, d + 1)       # the cache holds `last` and the ids of the path
+                stats["tokens"] += len(new)
+                out += new
+                history = torch.cat([history, torch.tensor(new[:-1], dtype=torch.long, device=history.device)])
+                continue
             pos = torch.arange(kv._seen_tokens, kv._seen_tokens + d + 1, device=self.device)[None]
             with kv.verifying():
                 argmax = self.model(cur, past_key_values=kv, use_cache=True, position_ids=pos).logits[0].argmax(-1)
