@@ -12,7 +12,7 @@
 //   contiguous per lane, no LDS); softmax state lives in registers (lane = one query row);
 //   O^T += V^T.P^T with V staged through a per-wave padded LDS tile and read back transposed by
 //   ds_read_b64_tr_b16 (types and tile constants: kvz_wave_tile.h).  A second kernel merges the head's partials.
-#include "kvz_wave_tile.h"
+#include "kvz_combine.h"
 
 namespace kvz {
 
@@ -249,9 +249,7 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
     }
 }
 
-// merge the partials of the key ranges.  grid = (Hkv, row tiles, 16 query rows); block = 1024 threads = (1024/D) slices of the
-// partials x D columns.  Every load of the main loop is independent (split-parallel): throughput-, not latency-bound.
-constexpr int CB_THREADS = 1024;
+// merge the partials of the key ranges.  grid = (Hkv, row tiles, 16 query rows); the body is combine_partials of kvz_combine.h.
 template <typename T, int D, bool HOSTMETA>
 __global__ __launch_bounds__(CB_THREADS) void varlen_attn_combine2_kernel(const float* __restrict__ part_o,
                                                                          const float* __restrict__ part_ml,
@@ -259,133 +257,21 @@ __global__ __launch_bounds__(CB_THREADS) void varlen_attn_combine2_kernel(const 
                                                                          const int32_t* __restrict__ k_len_offset_dev,
                                                                          HeadMeta hm, int Hkv, int G, int q_len, int target_items,
                                                                          int n_rtiles, T* __restrict__ out) {
-    constexpr int SLICES = CB_THREADS / D;
     if (k_len_offset_dev) k_len_offset += *k_len_offset_dev;
     const int h = blockIdx.x, rt = blockIdx.y, qq = blockIdx.z;
     const int R = q_len * G;
     if (rt * TILE_RT + qq >= R) return;
-    auto len_of = [&](int hh) -> int { return (HOSTMETA ? hm.len[hh] : k_len[hh]) + k_len_offset; };
-    int total = 0;
-    for (int hh = 0; hh < Hkv; ++hh) total += len_of(hh);
-    const int chunk = chunk_of(total, target_items);
-    int first_item = 0;
-    for (int hh = 0; hh < h; ++hh) first_item += max(1, (len_of(hh) + chunk - 1) / chunk);
-    const int nsp = max(1, (len_of(h) + chunk - 1) / chunk);
-    const int64_t base = ((int64_t)first_item * n_rtiles + rt) * TILE_RT + qq;  // + s * n_rtiles * TILE_RT
+    const ItemRange ir = item_range([&](int hh) -> int { return (HOSTMETA ? hm.len[hh] : k_len[hh]) + k_len_offset; }, Hkv, h,
+                                    target_items);
+    const int64_t base = ((int64_t)ir.first_item * n_rtiles + rt) * TILE_RT + qq;  // + s * n_rtiles * TILE_RT
     const int64_t istride = (int64_t)n_rtiles * TILE_RT;
-    const int tid = threadIdx.x;
-    const int d = tid % D, slice = tid / D;
-
-    __shared__ float s_red[CB_THREADS / WAVE];
-    __shared__ float s_acc[SLICES][D];
-    __shared__ float s_M, s_L;
-
-    constexpr int PER = 8;  // partials per thread on the fast path
-    if (nsp <= PER * SLICES) {
-        // ONE round trip to memory: every thread issues the loads of its (up to 8) partials - statistics and its column -
-        // before anything depends on them; the row maximum and the denominator are then block reductions over registers.
-        float2 ml[PER];
-        float ov[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int s2 = slice + i * SLICES;
-            const int64_t pi = base + (int64_t)min(s2, nsp - 1) * istride;
-            ml[i] = *reinterpret_cast<const float2*>(part_ml + pi * 2);
-            ov[i] = part_o[pi * D + d];
-            if (s2 >= nsp) ml[i] = make_float2(-INFINITY, 0.f);
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) mx = fmaxf(mx, ml[i].x);
-        mx = wave_reduce_max(mx);
-        if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-        __syncthreads();
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < CB_THREADS / WAVE; ++w) M = fmaxf(M, s_red[w]);
-        float acc = 0.f, lp = 0.f;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const float wgt = (ml[i].x == -INFINITY) ? 0.f : exp2f(ml[i].x - M);
-            acc += wgt * ov[i];
-            lp += wgt * ml[i].y;
-        }
-        s_acc[slice][d] = acc;
-        __syncthreads();  // (also: everybody has read s_red)
-        if (d == 0) s_red[slice] = lp;  // one thread per slice holds that slice's share of the denominator
-        __syncthreads();
-        if (tid < D) {
-            float a = 0.f, l = 0.f;
-#pragma unroll
-            for (int sl = 0; sl < SLICES; ++sl) { a += s_acc[sl][tid]; l += s_red[sl]; }
-            out[((int64_t)h * R + rt * TILE_RT + qq) * D + tid] = (T)((l > 0.f) ? a / l : 0.f);
-        }
-        return;
-    }
-    // general path (more partials than the fast path holds in registers): three dependent passes
-    float mx = -INFINITY;
-    for (int s2 = tid; s2 < nsp; s2 += CB_THREADS) mx = fmaxf(mx, part_ml[(base + s2 * istride) * 2]);
-    mx = wave_reduce_max(mx);
-    if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-    __syncthreads();
-    if (tid == 0) {
-        float m2 = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < CB_THREADS / WAVE; ++w) m2 = fmaxf(m2, s_red[w]);
-        s_M = m2;
-    }
-    __syncthreads();
-    const float M = s_M;
-    float lp = 0.f;
-    for (int s2 = tid; s2 < nsp; s2 += CB_THREADS) {
-        const float2 ml = *reinterpret_cast<const float2*>(part_ml + (base + s2 * istride) * 2);
-        lp += (ml.x == -INFINITY) ? 0.f : exp2f(ml.x - M) * ml.y;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lp += __shfl_xor(lp, o, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) s_red[tid >> 6] = lp;
-    __syncthreads();
-    if (tid == 0) {
-        float l2 = 0.f;
-#pragma unroll
-        for (int w = 0; w < CB_THREADS / WAVE; ++w) l2 += s_red[w];
-        s_L = l2;
-    }
-    float acc = 0.f;
-    for (int s2 = slice; s2 < nsp; s2 += SLICES) {
+    combine_partials<T, D>(ir.nsp, [&](int s2) -> Partial {
         const int64_t pi = base + s2 * istride;
-        const float ms = part_ml[pi * 2];
-        const float wgt = (ms == -INFINITY) ? 0.f : exp2f(ms - M);
-        acc += wgt * part_o[pi * D + d];
-    }
-    s_acc[slice][d] = acc;
-    __syncthreads();
-    if (tid < D) {
-        float a = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < SLICES; ++sl) a += s_acc[sl][tid];
-        const float l = s_L;
-        out[((int64_t)h * R + rt * TILE_RT + qq) * D + tid] = (T)((l > 0.f) ? a / l : 0.f);
-    }
+        return Partial{part_ml + pi * 2, part_o + pi * D};
+    }, out + ((int64_t)h * R + rt * TILE_RT + qq) * D);
 }
 
 __global__ void add_i32_kernel(int32_t* p, int delta) { *p += delta; }
-
-struct AttnWs { uint32_t* counters; float* part_ml; float* part_o; size_t bytes; };
-static inline AttnWs attn_ws(void* ws, int Hkv, int n_rtiles, int D) {
-    const size_t items = (size_t)target_items(Hkv) + Hkv;
-    AttnWs w;
-    char* p = reinterpret_cast<char*>(ws);
-    w.counters = reinterpret_cast<uint32_t*>(p);
-    p += align256((size_t)Hkv * n_rtiles * sizeof(uint32_t));
-    w.part_ml = reinterpret_cast<float*>(p);
-    p += align256(items * n_rtiles * TILE_RT * 2 * sizeof(float));
-    w.part_o = reinterpret_cast<float*>(p);
-    p += align256(items * n_rtiles * TILE_RT * D * sizeof(float));
-    w.bytes = (size_t)(p - reinterpret_cast<char*>(ws));
-    return w;
-}
 
 template <typename T, int D>
 static int launch_attn(const void* q, const void* k, const void* v, const int32_t* k_start, const int32_t* k_len,
@@ -393,7 +279,7 @@ static int launch_attn(const void* q, const void* k, const void* v, const int32_
                        void* ws, hipStream_t stream, const void* k_new = nullptr, const void* v_new = nullptr,
                        int64_t kn_stride = 0, int64_t vn_stride = 0) {
     const int n_rtiles = (q_len * G + TILE_RT - 1) / TILE_RT;
-    const AttnWs w = attn_ws(ws, Hkv, n_rtiles, D);
+    const SplitWs w = split_ws(ws, Hkv, n_rtiles, D);
     const int target = target_items(Hkv);
     HeadMeta hm;
     const bool host = meta_host != nullptr && Hkv <= AT_MAXH;
@@ -432,7 +318,7 @@ extern "C" size_t kvz_varlen_attn_workspace_bytes(int Hkv, int G, int q_len, int
     if (Hkv <= 0 || G <= 0 || q_len <= 0 || D <= 0 || max_len_k < 0) return 0;
     if (q_len * G > flash_min_rows()) return kvz_flash_workspace_bytes(Hkv, G, q_len, D) + 256;  // (never 0: callers pass a buffer)
     const int n_rtiles = (q_len * G + TILE_RT - 1) / TILE_RT;
-    return attn_ws(nullptr, Hkv, n_rtiles, D).bytes;
+    return split_ws(nullptr, Hkv, n_rtiles, D).bytes;
 }
 
 extern "C" int kvz_varlen_attn(const void* q, const void* k, const void* v, const int32_t* k_start,

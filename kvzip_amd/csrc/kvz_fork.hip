@@ -12,14 +12,14 @@
 //                        writes the branch's new K,V row to tail[b, h, tail_len[b]] (only this block reads that row; block-scope
 //                        barrier before the read) and attends the G rows of (b, h) over tail rows 0 .. tail_len[b].
 //   fork_combine_kernel  per (branch, head, group row): merges the partials of the head's key ranges and of the branch's tail.
-//                        Final normalisation: out = fp16/bf16(a / l)  (the 'div' form of tests/attn_probes.py, like the decode combine
-//                        of kvz_attn.hip); rows of an inactive branch (tail_len[b] < 0) are zero.
+//                        Final normalisation: out = fp16/bf16(a / l)  (the 'div' form of tests/attn_probes.py, as in every
+//                        caller of kvz_combine.h); rows of an inactive branch (tail_len[b] < 0) are zero.
 // No causal mask on the shared part: the whole context precedes every query.  The shared cache is never written.
 //
 // attn_merge_lse_kernel: merges two partial attention results by their natural-log LSEs (a branch's first step: kvz_flash_fwd over the
 // shared segments, causal = 0, and over the branch's tail, causal = 1):
 //   m = max(lse1, lse2);  w_i = exp(lse_i - m);  out = fp16/bf16((w1*o1 + w2*o2) / (w1 + w2));  both -inf -> 0.
-#include "kvz_wave_tile.h"
+#include "kvz_combine.h"
 
 #include <type_traits>
 
@@ -311,99 +311,35 @@ __global__ __launch_bounds__(FK_THREADS) void fork_attn_kernel(
     }
 }
 
-// merge, per (head, branch, group row), the partials of the head's key ranges and of the branch's tail.  grid = (Hkv, B, G);
-// block = 1024 threads = (1024/D) slices of the partials x D columns.  out = (T)(a / l).
-constexpr int CB_THREADS = 1024;
+// merge, per (head, branch, group row), the partials of the head's key ranges and of the branch's tail.  grid = (Hkv, B, G); the body
+// is combine_partials of kvz_combine.h.
 template <typename T, int D>
 __global__ __launch_bounds__(CB_THREADS) void fork_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                                                  const float* __restrict__ tail_o, const float* __restrict__ tail_ml,
                                                                  const int32_t* __restrict__ k_len, int k_len_offset, HeadMeta hm,
                                                                  int host_meta, TailLens tl, int B, int Hkv, int G, int target_items,
                                                                  int n_rtiles, T* __restrict__ out) {
-    constexpr int SLICES = CB_THREADS / D;
     const int h = blockIdx.x, b = blockIdx.y, g = blockIdx.z;
     const int tid = threadIdx.x;
-    const int d = tid % D, slice = tid / D;
     const int64_t orow = (((int64_t)b * Hkv + h) * G + g) * D;
     if (tl.n[b] < 0) {  // inactive branch
         if (tid < D) out[orow + tid] = (T)0.f;
         return;
     }
-    auto len_of = [&](int hh) -> int { return (host_meta ? hm.len[hh] : k_len[hh]) + k_len_offset; };
-    int total = 0;
-    for (int hh = 0; hh < Hkv; ++hh) total += len_of(hh);
-    const int chunk = chunk_of(total, target_items);
-    int first_item = 0;
-    for (int hh = 0; hh < h; ++hh) first_item += max(1, (len_of(hh) + chunk - 1) / chunk);
-    const int nsp = max(1, (len_of(h) + chunk - 1) / chunk);
+    const ItemRange ir = item_range([&](int hh) -> int { return (host_meta ? hm.len[hh] : k_len[hh]) + k_len_offset; }, Hkv, h,
+                                    target_items);
+    const int nsp = ir.nsp;
     const int r = b * G + g;
-    const int64_t base = ((int64_t)first_item * n_rtiles + r / TILE_RT) * TILE_RT + r % TILE_RT;
+    const int64_t base = ((int64_t)ir.first_item * n_rtiles + r / TILE_RT) * TILE_RT + r % TILE_RT;
     const int64_t istride = (int64_t)n_rtiles * TILE_RT;
     const int GT = (G + TILE_RT - 1) / TILE_RT;
     const int64_t trow = (((int64_t)b * Hkv + h) * GT + g / TILE_RT) * TILE_RT + g % TILE_RT;
-    const int n = nsp + 1;  // the key ranges of the head, then the branch's tail (an active branch has at least its new row)
-    auto ml_ptr = [&](int s2) -> const float* { return s2 < nsp ? part_ml + (base + s2 * istride) * 2 : tail_ml + trow * 2; };
-    auto o_ptr = [&](int s2) -> const float* { return s2 < nsp ? part_o + (base + s2 * istride) * D : tail_o + trow * D; };
-
-    __shared__ float s_red[CB_THREADS / WAVE];
-    __shared__ float s_acc[SLICES][D];
-    __shared__ float s_l[SLICES];
-
-    constexpr int PER = 8;  // partials per thread on the fast path
-    float acc = 0.f, lp = 0.f;
-    if (n <= PER * SLICES) {
-        // ONE round trip to memory: every thread issues the loads of its (up to 8) partials before anything depends on them
-        float2 ml[PER];
-        float ov[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int s2 = slice + i * SLICES;
-            const int sc = min(s2, n - 1);
-            ml[i] = *reinterpret_cast<const float2*>(ml_ptr(sc));
-            ov[i] = o_ptr(sc)[d];
-            if (s2 >= n) ml[i] = make_float2(-INFINITY, 0.f);
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) mx = fmaxf(mx, ml[i].x);
-        mx = wave_reduce_max(mx);
-        if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-        __syncthreads();
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < CB_THREADS / WAVE; ++w) M = fmaxf(M, s_red[w]);
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const float wgt = (ml[i].x == -INFINITY) ? 0.f : exp2f(ml[i].x - M);
-            acc += wgt * ov[i];
-            lp += wgt * ml[i].y;
-        }
-    } else {
-        // more partials than the fast path holds in registers: the maximum first, then one pass over the partials
-        float mx = -INFINITY;
-        for (int s2 = tid; s2 < n; s2 += CB_THREADS) mx = fmaxf(mx, ml_ptr(s2)[0]);
-        mx = wave_reduce_max(mx);
-        if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-        __syncthreads();
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < CB_THREADS / WAVE; ++w) M = fmaxf(M, s_red[w]);
-        for (int s2 = slice; s2 < n; s2 += SLICES) {
-            const float2 ml = *reinterpret_cast<const float2*>(ml_ptr(s2));
-            const float wgt = (ml.x == -INFINITY) ? 0.f : exp2f(ml.x - M);
-            acc += wgt * o_ptr(s2)[d];
-            lp += wgt * ml.y;
-        }
-    }
-    s_acc[slice][d] = acc;
-    if (d == 0) s_l[slice] = lp;  // (every column of a slice holds the same share of the denominator)
-    __syncthreads();
-    if (tid < D) {
-        float a = 0.f, l = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < SLICES; ++sl) { a += s_acc[sl][tid]; l += s_l[sl]; }
-        out[orow + tid] = (T)((l > 0.f) ? a / l : 0.f);
-    }
+    // the key ranges of the head, then the branch's tail (an active branch has at least its new row)
+    combine_partials<T, D>(nsp + 1, [&](int s2) -> Partial {
+        if (s2 >= nsp) return Partial{tail_ml + trow * 2, tail_o + trow * D};
+        const int64_t pi = base + s2 * istride;
+        return Partial{part_ml + pi * 2, part_o + pi * D};
+    }, out + orow);
 }
 
 // out[r, :] = merge of (o1[r, :], lse1[r]) and (o2[r, :], lse2[r]); one thread per 8 elements (16 bytes)

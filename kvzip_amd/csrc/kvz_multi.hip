@@ -22,7 +22,7 @@
 // nothing to keep in step with the caches.  A block finds its (segment, key range) with wave-uniform scalar work from those prefixes
 // (up to 127 compares against constant kernel-argument offsets): batches of scalar loads from the kernel-argument segment, independent of
 // each other.
-#include "kvz_wave_tile.h"
+#include "kvz_combine.h"
 #include "../../include/kvzip_hip_multi.h"
 
 #include <limits.h>
@@ -247,16 +247,13 @@ __global__ __launch_bounds__(MK_THREADS) void multi_attn_split_kernel(
     }
 }
 
-// merge, per (segment, group row), the partials of the segment's key ranges.  grid = (S, G); block = 1024 threads = (1024/D) slices of
-// the partials x D columns.  out = (T)(a / l); rows of an inactive cache are zero.
-constexpr int CB_THREADS = 1024;
+// merge, per (segment, group row), the partials of the segment's key ranges.  grid = (S, G); the body is combine_partials of
+// kvz_combine.h.  Rows of an inactive cache are zero.
 template <typename T, int D>
 __global__ __launch_bounds__(CB_THREADS) void multi_attn_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                                                        Table tb, int Hkv, int G, int n_rtiles, T* __restrict__ out) {
-    constexpr int SLICES = CB_THREADS / D;
     const int s = blockIdx.x, g = blockIdx.y;
     const int tid = threadIdx.x;
-    const int d = tid % D, slice = tid / D;
     const int64_t orow = ((int64_t)s * G + g) * D;
     if (tb.off[s / Hkv] < 0) {  // inactive cache
         if (tid < D) out[orow + tid] = (T)0.f;
@@ -266,67 +263,10 @@ __global__ __launch_bounds__(CB_THREADS) void multi_attn_combine_kernel(const fl
     const int n = tb.item0[s + 1] - first_item;   // (>= 1: every segment of a live cache has an item)
     const int64_t base = ((int64_t)first_item * n_rtiles + g / TILE_RT) * TILE_RT + g % TILE_RT;
     const int64_t istride = (int64_t)n_rtiles * TILE_RT;
-
-    __shared__ float s_red[CB_THREADS / WAVE];
-    __shared__ float s_acc[SLICES][D];
-    __shared__ float s_l[SLICES];
-
-    constexpr int PER = 8;  // partials per thread on the fast path
-    float acc = 0.f, lp = 0.f;
-    if (n <= PER * SLICES) {
-        // ONE round trip to memory: every thread issues the loads of its (up to 8) partials before anything depends on them
-        float2 ml[PER];
-        float ov[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int s2 = slice + i * SLICES;
-            const int64_t pi = base + (int64_t)min(s2, n - 1) * istride;
-            ml[i] = *reinterpret_cast<const float2*>(part_ml + pi * 2);
-            ov[i] = part_o[pi * D + d];
-            if (s2 >= n) ml[i] = make_float2(-INFINITY, 0.f);
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) mx = fmaxf(mx, ml[i].x);
-        mx = wave_reduce_max(mx);
-        if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-        __syncthreads();
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < CB_THREADS / WAVE; ++w) M = fmaxf(M, s_red[w]);
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const float wgt = (ml[i].x == -INFINITY) ? 0.f : exp2f(ml[i].x - M);
-            acc += wgt * ov[i];
-            lp += wgt * ml[i].y;
-        }
-    } else {
-        // more partials than the fast path holds in registers: the maximum first, then one pass over the partials
-        float mx = -INFINITY;
-        for (int s2 = tid; s2 < n; s2 += CB_THREADS) mx = fmaxf(mx, part_ml[(base + s2 * istride) * 2]);
-        mx = wave_reduce_max(mx);
-        if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-        __syncthreads();
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < CB_THREADS / WAVE; ++w) M = fmaxf(M, s_red[w]);
-        for (int s2 = slice; s2 < n; s2 += SLICES) {
-            const int64_t pi = base + s2 * istride;
-            const float2 ml = *reinterpret_cast<const float2*>(part_ml + pi * 2);
-            const float wgt = (ml.x == -INFINITY) ? 0.f : exp2f(ml.x - M);
-            acc += wgt * part_o[pi * D + d];
-            lp += wgt * ml.y;
-        }
-    }
-    s_acc[slice][d] = acc;
-    if (d == 0) s_l[slice] = lp;  // (every column of a slice holds the same share of the denominator)
-    __syncthreads();
-    if (tid < D) {
-        float a = 0.f, l = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < SLICES; ++sl) { a += s_acc[sl][tid]; l += s_l[sl]; }
-        out[orow + tid] = (T)((l > 0.f) ? a / l : 0.f);
-    }
+    combine_partials<T, D>(n, [&](int s2) -> Partial {
+        const int64_t pi = base + s2 * istride;
+        return Partial{part_ml + pi * 2, part_o + pi * D};
+    }, out + orow);
 }
 
 struct MultiWs { float* part_ml; float* part_o; size_t items; size_t bytes; };

@@ -9,7 +9,7 @@
 //                          from the index: the same cut into work items over the SUM of the head lengths, the same 32-key wave tile, the same
 //                          merge of the 8 waves.  The arithmetic - expressions and their order - is that of kvz_attn.hip, so the result
 //                          is the bits of kvz_varlen_attn on the compacted copy.
-//   retain_combine_kernel  the combine of kvz_attn.hip on by-value metadata.
+//   retain_combine_kernel  combine_partials of kvz_combine.h over the head's key ranges, on by-value metadata.
 // The steps of the wave tile are spelled out here as in every kernel on kvz_wave_tile.h.
 //
 // Positions.  A lane holds the position of ONE key of a tile (key t0 + (lane & 31)); the K and V loads take theirs through a lane
@@ -17,7 +17,7 @@
 // is a dependent load in front of the row loads: the positions of tile t + 2*T_STEP are requested before the rows of tile t + T_STEP,
 // whose positions were requested one iteration earlier and have arrived since.  Like the row loads they are issued unconditionally
 // (clamped keys), so the loop has no load under a branch (see the comment above the key loop of kvz_attn.hip).
-#include "kvz_wave_tile.h"
+#include "kvz_combine.h"
 #include "../../include/kvzip_hip_retain.h"
 
 namespace kvz {
@@ -288,136 +288,21 @@ __global__ __launch_bounds__(RT_THREADS) void retain_attn_kernel(
     }
 }
 
-// merge the partials of the key ranges.  grid = (Hkv, row tiles, 16 query rows); block = 1024 threads = (1024/D) slices of the
-// partials x D columns (varlen_attn_combine2_kernel of kvz_attn.hip on by-value metadata).
-constexpr int CB_THREADS = 1024;
+// merge the partials of the key ranges.  grid = (Hkv, row tiles, 16 query rows); the body is combine_partials of kvz_combine.h.
 template <typename T, int D>
 __global__ __launch_bounds__(CB_THREADS) void retain_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                                                    HeadMeta hm, int tail, int Hkv, int G, int q_len, int target_items,
                                                                    int n_rtiles, T* __restrict__ out) {
-    constexpr int SLICES = CB_THREADS / D;
     const int h = blockIdx.x, rt = blockIdx.y, qq = blockIdx.z;
     const int R = q_len * G;
     if (rt * TILE_RT + qq >= R) return;
-    auto len_of = [&](int hh) -> int { return hm.cnt[hh] + tail; };
-    int total = 0;
-    for (int hh = 0; hh < Hkv; ++hh) total += len_of(hh);
-    const int chunk = chunk_of(total, target_items);
-    int first_item = 0;
-    for (int hh = 0; hh < h; ++hh) first_item += max(1, (len_of(hh) + chunk - 1) / chunk);
-    const int nsp = max(1, (len_of(h) + chunk - 1) / chunk);
-    const int64_t base = ((int64_t)first_item * n_rtiles + rt) * TILE_RT + qq;  // + s * n_rtiles * TILE_RT
+    const ItemRange ir = item_range([&](int hh) -> int { return hm.cnt[hh] + tail; }, Hkv, h, target_items);
+    const int64_t base = ((int64_t)ir.first_item * n_rtiles + rt) * TILE_RT + qq;  // + s * n_rtiles * TILE_RT
     const int64_t istride = (int64_t)n_rtiles * TILE_RT;
-    const int tid = threadIdx.x;
-    const int d = tid % D, slice = tid / D;
-
-    __shared__ float s_red[CB_THREADS / WAVE];
-    __shared__ float s_acc[SLICES][D];
-    __shared__ float s_M, s_L;
-
-    constexpr int PER = 8;  // partials per thread on the fast path
-    if (nsp <= PER * SLICES) {
-        // ONE round trip to memory: every thread issues the loads of its (up to 8) partials - statistics and its column -
-        // before anything depends on them; the row maximum and the denominator are then block reductions over registers.
-        float2 ml[PER];
-        float ov[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int s2 = slice + i * SLICES;
-            const int64_t pi = base + (int64_t)min(s2, nsp - 1) * istride;
-            ml[i] = *reinterpret_cast<const float2*>(part_ml + pi * 2);
-            ov[i] = part_o[pi * D + d];
-            if (s2 >= nsp) ml[i] = make_float2(-INFINITY, 0.f);
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) mx = fmaxf(mx, ml[i].x);
-        mx = wave_reduce_max(mx);
-        if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-        __syncthreads();
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < CB_THREADS / WAVE; ++w) M = fmaxf(M, s_red[w]);
-        float acc = 0.f, lp = 0.f;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const float wgt = (ml[i].x == -INFINITY) ? 0.f : exp2f(ml[i].x - M);
-            acc += wgt * ov[i];
-            lp += wgt * ml[i].y;
-        }
-        s_acc[slice][d] = acc;
-        __syncthreads();  // (also: everybody has read s_red)
-        if (d == 0) s_red[slice] = lp;  // one thread per slice holds that slice's share of the denominator
-        __syncthreads();
-        if (tid < D) {
-            float a = 0.f, l = 0.f;
-#pragma unroll
-            for (int sl = 0; sl < SLICES; ++sl) { a += s_acc[sl][tid]; l += s_red[sl]; }
-            out[((int64_t)h * R + rt * TILE_RT + qq) * D + tid] = (T)((l > 0.f) ? a / l : 0.f);
-        }
-        return;
-    }
-    // general path (more partials than the fast path holds in registers): three dependent passes
-    float mx = -INFINITY;
-    for (int s2 = tid; s2 < nsp; s2 += CB_THREADS) mx = fmaxf(mx, part_ml[(base + s2 * istride) * 2]);
-    mx = wave_reduce_max(mx);
-    if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-    __syncthreads();
-    if (tid == 0) {
-        float m2 = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < CB_THREADS / WAVE; ++w) m2 = fmaxf(m2, s_red[w]);
-        s_M = m2;
-    }
-    __syncthreads();
-    const float M = s_M;
-    float lp = 0.f;
-    for (int s2 = tid; s2 < nsp; s2 += CB_THREADS) {
-        const float2 ml = *reinterpret_cast<const float2*>(part_ml + (base + s2 * istride) * 2);
-        lp += (ml.x == -INFINITY) ? 0.f : exp2f(ml.x - M) * ml.y;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lp += __shfl_xor(lp, o, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) s_red[tid >> 6] = lp;
-    __syncthreads();
-    if (tid == 0) {
-        float l2 = 0.f;
-#pragma unroll
-        for (int w = 0; w < CB_THREADS / WAVE; ++w) l2 += s_red[w];
-        s_L = l2;
-    }
-    float acc = 0.f;
-    for (int s2 = slice; s2 < nsp; s2 += SLICES) {
+    combine_partials<T, D>(ir.nsp, [&](int s2) -> Partial {
         const int64_t pi = base + s2 * istride;
-        const float ms = part_ml[pi * 2];
-        const float wgt = (ms == -INFINITY) ? 0.f : exp2f(ms - M);
-        acc += wgt * part_o[pi * D + d];
-    }
-    s_acc[slice][d] = acc;
-    __syncthreads();
-    if (tid < D) {
-        float a = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < SLICES; ++sl) a += s_acc[sl][tid];
-        const float l = s_L;
-        out[((int64_t)h * R + rt * TILE_RT + qq) * D + tid] = (T)((l > 0.f) ? a / l : 0.f);
-    }
-}
-
-// the workspace layout of kvz_attn.hip (attn_ws), byte for byte: a reserved region, the statistics, the partial outputs
-struct RetainWs { float* part_ml; float* part_o; size_t bytes; };
-static inline RetainWs retain_ws(void* ws, int Hkv, int n_rtiles, int D) {
-    const size_t items = (size_t)target_items(Hkv) + Hkv;
-    RetainWs w;
-    char* p = reinterpret_cast<char*>(ws);
-    p += align256((size_t)Hkv * n_rtiles * sizeof(uint32_t));
-    w.part_ml = reinterpret_cast<float*>(p);
-    p += align256(items * n_rtiles * TILE_RT * 2 * sizeof(float));
-    w.part_o = reinterpret_cast<float*>(p);
-    p += align256(items * n_rtiles * TILE_RT * D * sizeof(float));
-    w.bytes = (size_t)(p - reinterpret_cast<char*>(ws));
-    return w;
+        return Partial{part_ml + pi * 2, part_o + pi * D};
+    }, out + ((int64_t)h * R + rt * TILE_RT + qq) * D);
 }
 
 template <typename T, int D>
@@ -426,7 +311,7 @@ static int launch_retain(const void* q, const void* k, const void* v, int64_t he
                          void* out, void* ws, hipStream_t stream, const void* k_new = nullptr, const void* v_new = nullptr,
                          int64_t kn_stride = 0, int64_t vn_stride = 0) {
     const int n_rtiles = (q_len * G + TILE_RT - 1) / TILE_RT;
-    const RetainWs w = retain_ws(ws, Hkv, n_rtiles, D);
+    const SplitWs w = split_ws(ws, Hkv, n_rtiles, D);  // (the layout of kvz_varlen_attn)
     const int target = target_items(Hkv);
     HeadMeta hm;
     for (int h = 0; h < RT_MAXH; ++h) {
@@ -490,7 +375,7 @@ extern "C" size_t kvz_retain_attn_workspace_bytes(int Hkv, int G, int q_len, int
     if (Hkv <= 0 || G <= 0 || q_len <= 0 || D <= 0) return 0;
     if ((int64_t)q_len * G > retain_max_rows()) return 0;
     const int n_rtiles = (q_len * G + TILE_RT - 1) / TILE_RT;
-    return retain::retain_ws(nullptr, Hkv, n_rtiles, D).bytes;
+    return split_ws(nullptr, Hkv, n_rtiles, D).bytes;
 }
 
 // the checks the two attention calls share; `rows` = rows of a head that are read (fill, + 1 with the append), `tail` the keys behind the

@@ -38,7 +38,9 @@ __global__ __launch_bounds__(SP_THREADS) void spec_attn_kernel(
 }
 
 // merge, per (head, position, group row), the partials of the head's key ranges and of its triangle.  grid = (Hkv, t, G);
-// block = 1024 threads = (1024/D) slices of the partials x D columns.  out = (T)(a / l).
+// block = 1024 threads = (1024/D) slices of the partials x D columns.  out = (T)(a / l).  This is combine_partials of kvz_combine.h
+// spelled out: the other four combine kernels call it, this one exceeded the timing margin when it did and no cause was found
+// (profiles/combine_shared_ab.txt).  A fix to the combine is made in both places.
 constexpr int CB_THREADS = 1024;
 template <typename T, int D>
 __global__ __launch_bounds__(CB_THREADS) void spec_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,

@@ -7,8 +7,9 @@
 //   softmax       online, fp32, in the exp2 domain, state in registers;
 //   O^T += V^T.P^T with the V rows staged through a padded per-wave LDS tile (VSTRIDE) and read back transposed by ds_read_b64_tr_b16.
 // The steps of the tile themselves (Q fragment, clamped K and V loads, V staging, products, softmax update, read-back, the merge of a
-// block's waves, the combine) are spelled out in every kernel: as calls into shared functions each of them - even the V staging alone,
-// even with the lane handed in - moved the compiler's schedule of the key loop of the decode kernel.
+// block's waves) are spelled out in every kernel: as calls into shared functions each of them - even the V staging alone, even with
+// the lane handed in - moved the compiler's schedule of the key loop of the decode kernel.  The combine of the
+// partials, a launch of its own, is shared: kvz_combine.h.
 #pragma once
 #include "kvz_common.h"
 

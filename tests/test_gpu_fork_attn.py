@@ -94,6 +94,29 @@ def test_weighted_probe_exact(G, B, D, dtype):
         _check_exact(f"weighted G{G} B{B} D{D} {dtype}", c)
 
 
+BOUNDARY_KEYS = {128: (8064, 8192), 64: (16256, 16384)}     # shared keys of the long head: 8 * 1024 / D - 1 key ranges of 128 keys, and one more
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("G,D", [(7, 128), (4, 64)])
+def test_combine_at_the_boundary_between_its_two_paths(G, D, dtype):
+    """The combine holds up to 8 partials per thread in registers (8 * 1024 / D per row) and takes its general path beyond.  With
+    attn_items = 1024 a key range is its 128-key minimum, so a head of 8064 shared keys (D = 128; 16256 at D = 64) has, with the
+    branch's tail, the last partial count of the fast path and a head of one range more the first of the general path.  The heads beside
+    it have 1 and 0 keys (1 and 1 in the weighted case, which needs a key in every shared segment).  B = 2; a second call with branch 1
+    inactive.  Split edges marked; both probe families."""
+    B, cap = 2, 64
+    with knob("attn_items", 1024):
+        target = fp.fork_items(1024, B, 3, G)
+        for n, partials in zip(BOUNDARY_KEYS[D], (8 * 1024 // D, 8 * 1024 // D + 1)):
+            assert ap.decode_chunk([n, 1, 1], target) == 128 and n % 128 == 0 and n // 128 + 1 == partials
+            for tl in ([37, 0], [37, -1]):
+                _check_exact(f"uniform boundary {n} keys D{D} {dtype} tails {tl}",
+                             fp.uniform_case([n, 1, 0], B, G, D, dtype, tl, cap, items=(target,), seed=n))
+                _check_exact(f"weighted boundary {n} keys D{D} {dtype} tails {tl}",
+                             fp.weighted_case([n, 1, 1], B, G, D, dtype, tl, cap, seed=n))
+
+
 @pytest.mark.parametrize("kind", ["uniform", "weighted"])
 def test_offset_metadata_forms_and_default_items(kind):
     """A non-zero k_len_offset (rows a multi-turn update appended before the fork), head segments by value and / or as device arrays,

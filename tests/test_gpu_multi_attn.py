@@ -105,6 +105,28 @@ def test_inactive_cache(kind, items):
     assert bool((out == 0).all())
 
 
+BOUNDARY_KEYS = {128: (8192, 8193), 64: (16384, 16385)}     # keys of the long segment: 8 * 1024 / D key ranges of 128 keys, and one more
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("G,D", [(7, 128), (4, 64)])
+def test_combine_at_the_boundary_between_its_two_paths(G, D, dtype):
+    """The combine holds up to 8 partials per thread in registers (8 * 1024 / D per row) and takes its general path beyond.  With
+    attn_items = 1024 a key range is its 128-key minimum, so a segment of 8192 keys, the new row included (D = 128; 16384 at D = 64),
+    has the last partial count of the fast path and a segment of one key more the first of the general path.  Two caches, the segments
+    beside the long one of 1, 0 and 37 base rows; a second call with the second cache inactive.  Split edges marked; both families."""
+    with knob("attn_items", 1024):
+        for n, partials in zip(BOUNDARY_KEYS[D], (8 * 1024 // D, 8 * 1024 // D + 1)):
+            lens = [[n - 1, 1], [0, 37]]
+            for off in ([0, 0], [0, -1]):
+                for c in (mp.uniform_case(lens, off, G, D, dtype, SLACK, items=(1024,), seed=n),
+                          mp.weighted_case(lens, off, G, D, dtype, SLACK, seed=n)):
+                    seg = c.segment_lengths()
+                    assert seg[0] == n and ap.decode_chunk(seg, mp.multi_items(1024, 4)) == 128 and -(-n // 128) == partials
+                    out = _check_exact(f"{c.kind} boundary {n} keys D{D} {dtype} offsets {off}", c)
+                    assert off[1] >= 0 or bool((out[1] == 0).all())
+
+
 def _check_oracle(name, c):
     out, ak, av = _run(c)
     ek, ev = mp.expected_arenas(c)

@@ -133,6 +133,35 @@ def test_range_edge_at_the_end_of_the_index():
                 assert ap.bits_equal(got, ap.expected(p, "div"))[0], (p.kind, q_len, tail0)
 
 
+BOUNDARY_KEYS = {128: (8192, 8193), 64: (16384, 16385)}     # keys of the long head: 8 * 1024 / D key ranges of 128 keys, and one more
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f16", "bf16"])
+@pytest.mark.parametrize("G,D", [(7, 128), (4, 64)])
+def test_combine_at_the_boundary_between_its_two_paths(G, D, dtype):
+    """The combine holds up to 8 partials per thread in registers (8 * 1024 / D per row) and takes its general path beyond.  With
+    attn_items = 1024 a key range is its 128-key minimum, so a head of 8192 keys (D = 128; 16384 at D = 64) has the last partial count
+    of the fast path and a head of one key more the first of the general path.  The heads beside it have one key (the query's own
+    row: every head of a dense cache has the tail) and two.  Split edges marked; both probe families, plain and append form."""
+    n_ctx = BOUNDARY_KEYS[D][1] + 100
+    for n, partials in zip(BOUNDARY_KEYS[D], (8 * 1024 // D, 8 * 1024 // D + 1)):
+        one = torch.zeros(n_ctx, dtype=torch.bool)
+        one[n_ctx // 2] = True
+        masks = [rp.make_masks(n_ctx, seed=n, kinds=("random",), random_kept=n - 1)[0], torch.zeros(n_ctx, dtype=torch.bool), one]
+        lens = rp.head_lens(masks, 0, 1)
+        assert lens == [n, 1, 2] and ap.decode_chunk(lens, 1024) == 128 and -(-n // 128) == partials
+        for p in (ap.uniform_probe(lens, 1, G, D, dtype, items=(1024,), slack=0, seed=n),
+                  ap.weighted_probe(lens, 1, G, D, dtype, slack=0, seed=n)):
+            want = ap.expected(p, "div")
+            d = rp.scatter(p, masks, 0, 1)
+            with knob("attn_items", 1024):
+                got = _attend(d, p)
+                assert ap.bits_equal(got, want)[0], (p.kind, n, int(ap.steps(got, want).max()))
+                got, k, v = _append(d, p)
+                assert ap.bits_equal(got, want)[0], (p.kind, n, "append form", int(ap.steps(got, want).max()))
+                assert _same_bits(k, d.k) and _same_bits(v, d.v), (p.kind, n, "append form: the store afterwards")
+
+
 def _gather_route(p):
     """kvz_varlen_attn on the compacted copy (the probe's own flat rows, no slack), metadata on the device as RetainCache.prepare
     hands it over."""

@@ -106,6 +106,29 @@ def test_offset_metadata_forms_items_and_empty_head(kind):
                 _check_exact(f"{kind} empty head items {items} G{G} t{t}", make(LENS_EMPTY, t, G, D, torch.float16, seed=9))
 
 
+BOUNDARY_KEYS = {128: (8064, 8192), 64: (16256, 16384)}     # old rows of the long head: 8 * 1024 / D - 1 key ranges of 128 keys, and one more
+
+
+def boundary_cases(G, D, dtype, t=3):
+    """(name, case) at the boundary between the two paths of the combine, under attn_items = 1024 (also for the tree form): a head
+    whose old rows are 8 * 1024 / D - 1 key ranges of 128 keys, and one range more, beside heads of 1 and 0 rows; with the triangle
+    that is the last partial count the combine holds in registers and the first of its general path.  Split edges marked."""
+    target = sp.spec_items(1024, 3)
+    for n, partials in zip(BOUNDARY_KEYS[D], (8 * 1024 // D, 8 * 1024 // D + 1)):
+        lens = [n, 1, 0]
+        assert ap.decode_chunk(lens, target) == 128 and n % 128 == 0 and n // 128 + 1 == partials
+        yield f"uniform boundary {n} rows D{D} {dtype}", sp.uniform_case(lens, t, G, D, dtype, items=(target,), seed=n)
+        yield f"weighted boundary {n} rows D{D} {dtype}", sp.weighted_case(lens, t, G, D, dtype, seed=n)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("G,D", [(7, 128), (4, 64)])
+def test_combine_at_the_boundary_between_its_two_paths(G, D, dtype):
+    with knob("attn_items", 1024):
+        for name, c in boundary_cases(G, D, dtype):
+            _check_exact(name, c)
+
+
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
 @pytest.mark.parametrize("G,t,D", [(7, 2, 128), (7, 5, 128), (7, 9, 128), (4, 16, 128), (2, 3, 64)])
 def test_oracle_parity_random(G, t, D, dtype):

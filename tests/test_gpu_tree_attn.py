@@ -9,7 +9,7 @@ import kvzip_oracle as orc
 import spec_probes as sp
 import tree_probes as tp
 from conftest import check_attn
-from test_gpu_spec_attn import DEV, ITEMS, LENS, LENS_EMPTY, TOL, _new_rows, _ops, knob
+from test_gpu_spec_attn import DEV, ITEMS, LENS, LENS_EMPTY, TOL, _new_rows, _ops, boundary_cases, knob
 from test_gpu_spec_attn import _run as _run_chain
 
 pytestmark = pytest.mark.gpu
@@ -81,6 +81,17 @@ def test_offset_metadata_forms_items_and_empty_head(kind):
                 for tree in ("star", "random"):
                     _check_exact(f"{kind} empty head items {items} G{G} t{t} {tree}", make(LENS_EMPTY, t, G, D, torch.float16, seed=9),
                                  tp.parents_of(tree, t))
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("G,D", [(7, 128), (4, 64)])
+def test_combine_at_the_boundary_between_its_two_paths(G, D, dtype):
+    """The cases of the chain form's test of this name (the last partial count of the combine's fast path and the first of its general
+    path), on a star and on an interleaved tree of t = 3 nodes."""
+    with knob("attn_items", 1024):
+        for name, c in boundary_cases(G, D, dtype):
+            for kind in ("star", "interleaved"):
+                _check_exact(f"{name} {kind}", c, tp.parents_of(kind, 3))
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
