@@ -83,34 +83,19 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
     const int wave = threadIdx.x >> 6;
     const int l15 = lane & 15, quad = lane >> 4;
 
+    constexpr int BLOCK_WAVES = AT_WAVES;
     __shared__ __attribute__((aligned(16))) char lds[AT_WAVES * C::WAVE_LDS];
     char* wl = lds + wave * C::WAVE_LDS;
 
-    // ---- stationary Q fragment (B operand of S^T = K.Q^T): col = query row, k = head-dim slice ----
-    const int qrow = rt * TILE_RT + l15;
-    const bool qvalid = qrow < R;
-    v8 qf[C::KK];
-    {
-        const T* qp = q + ((int64_t)h * R + (qvalid ? qrow : 0)) * D + quad * 8;
-#pragma unroll
-        for (int kk = 0; kk < C::KK; ++kk) {
-            u32x4 raw = *reinterpret_cast<const u32x4*>(qp + kk * 32);
-            if (!qvalid) raw = u32x4{0, 0, 0, 0};
-            qf[kk] = __builtin_bit_cast(v8, raw);
-        }
-    }
+    const int n_qrows = R;
+    const int64_t q_row0 = (int64_t)h * R;
+#include "kvz_decode_state.inc"
     int limit = causal ? (qrow / G) + len - q_len : len - 1;  // last visible key of this lane's query row (bottom-right aligned)
     if (!qvalid) limit = -1;
-
+    auto visible = [&](int key) -> bool { return key <= limit && key < c1; };
+    // (behind `limit`, where they always stood: the order of a kernel's statements is part of what the compiler sees)
     const char* kbase = reinterpret_cast<const char*>(k) + seg * C::ROW_BYTES;
     const char* vbase = reinterpret_cast<const char*>(v) + seg * C::ROW_BYTES;
-
-    float m_run = -INFINITY, l_run = 0.f;
-    f4 o[C::DB];
-#pragma unroll
-    for (int i = 0; i < C::DB; ++i) o[i] = f4{0.f, 0.f, 0.f, 0.f};
-    const float sl2 = scale * LOG2E;  // work in the exp2 domain
-
     auto load_tile = [&](u32x4 (&kr)[2][C::KK], u32x4 (&vr)[C::VLOADS], int t0) {
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
@@ -128,125 +113,11 @@ __global__ __launch_bounds__(AT_THREADS) void varlen_attn_split2_kernel(
             vr[it] = *reinterpret_cast<const u32x4*>(vbase + (int64_t)key * C::ROW_BYTES + (c % C::CPR) * 16);
         }
     };
-    u32x4 kraw[2][C::KK], vraw[C::VLOADS], knext[2][C::KK], vnext[C::VLOADS];
-    // one 32-key tile of this wave: S^T = K.Q^T, online softmax, V through the wave's LDS tile, O^T += V^T.P^T
-    auto compute_tile = [&](const u32x4 (&kr)[2][C::KK], const u32x4 (&vr)[C::VLOADS], int t0) __attribute__((always_inline)) {
-        f4 s[2];
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-            s[sub] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < C::KK; ++kk)
-                s[sub] = Half<T>::mfma(__builtin_bit_cast(v8, kr[sub][kk]), qf[kk], s[sub]);
-        }
-#pragma unroll
-        for (int it = 0; it < C::VLOADS; ++it) {
-            const int c = it * WAVE + lane;
-            *reinterpret_cast<u32x4*>(wl + (c / C::CPR) * C::VSTRIDE + (c % C::CPR) * 16) = vr[it];
-        }
-        float sv[8];
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int key = t0 + (j >> 2) * 16 + quad * 4 + (j & 3);
-            float x = s[j >> 2][j & 3] * sl2;
-            x = (key <= limit && key < c1) ? x : -INFINITY;
-            sv[j] = x;
-            tmax = fmaxf(tmax, x);
-        }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float m_new = fmaxf(m_run, tmax);
-        const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = exp2f(m_run - m_safe);
-        float psum = 0.f;
-        v8 pb;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float p = exp2f(sv[j] - m_safe);
-            psum += p;
-            pb[j] = (T)p;
-        }
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int i = 0; i < C::DB; ++i) {
-            o[i][0] *= alpha; o[i][1] *= alpha; o[i][2] *= alpha; o[i][3] *= alpha;
-        }
-        const char* trp = wl + (quad * 4 + (l15 >> 2)) * C::VSTRIDE + (l15 & 3) * 8;
-#pragma unroll
-        for (int db = 0; db < C::DB; ++db) {
-            s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(trp + db * 32));
-            s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(trp + 16 * C::VSTRIDE + db * 32));
-            s8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            o[db] = Half<T>::mfma(__builtin_bit_cast(v8, both), pb, o[db]);
-        }
-    };
-    // The wave's tiles, one requested AHEAD of the one being computed.  Round 4: the steady-state loop issues the next tile's loads
-    // UNCONDITIONALLY and the last tile is computed after the loop.  With the request inside `if (tn < c1)` the compiler has to place
-    // waits that are right on both paths - s_waitcnt vmcnt(7) .. vmcnt(0) before the V rows of the CURRENT tile go to LDS - which
-    // drains the tile that has just been requested in the middle of every iteration: no load was ever in flight while a wave
-    // computed, and the kernel ran at 21 us where the bare read stream takes 12.5 (profiles/r4_probe_stream.txt).
-    const int t_first = c0 + wave * TILE_KT;
-    constexpr int T_STEP = AT_WAVES * TILE_KT;
-    if (t_first < c1) {
-        load_tile(kraw, vraw, t_first);
-        int t0 = t_first;
-#pragma unroll 1
-        for (; t0 + T_STEP < c1; t0 += T_STEP) {
-            load_tile(knext, vnext, t0 + T_STEP);
-            compute_tile(kraw, vraw, t0);
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int kk = 0; kk < C::KK; ++kk) kraw[sub][kk] = knext[sub][kk];
-#pragma unroll
-            for (int it = 0; it < C::VLOADS; ++it) vraw[it] = vnext[it];
-        }
-        compute_tile(kraw, vraw, t0);
-    }
-
-    // ---- merge the 8 waves of the block through LDS (each wave writes only its own region) ----------
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
-    // Rows of D + 4 floats: with a stride of D floats (512 B) the 16 lanes of a quad - 16 query rows, the same output columns -
-    // all hit one LDS bank (round 5: 16-way conflict on every store, ~1 us per block, found by ablation: profiles/r5_decode_ablation.txt);
-    // the padded row puts the 16-byte stores of 8 consecutive query rows on 8 different bank groups.  Only valid query rows are
-    // written and merged (decode: G of the 16).
-    constexpr int WSTR = D + 4;                          // floats per staged row
-    static_assert((TILE_RT * WSTR + 2 * TILE_RT) * 4 <= C::WAVE_LDS, "the wave's V tile holds its merge staging");
-    float* wo = reinterpret_cast<float*>(wl);            // [16 q][D + 4]
-    float* wm = wo + TILE_RT * WSTR;                       // [16] m, [16] l
-    const int rows_valid = min(TILE_RT, R - rt * TILE_RT);
-    if (l15 < rows_valid) {
-#pragma unroll
-        for (int db = 0; db < C::DB; ++db) *reinterpret_cast<f4*>(wo + l15 * WSTR + db * 16 + quad * 4) = o[db];
-        if (quad == 0) { wm[l15] = m_run; wm[16 + l15] = l_run; }
-    }
-    __syncthreads();
+#include "kvz_decode_step.inc"
+#include "kvz_decode_loop.inc"
 
     const int64_t pbase = ((int64_t)(first_item + split) * n_rtiles + rt) * TILE_RT;  // partial slot of this item
-    for (int e = threadIdx.x; e < rows_valid * (D / 4); e += AT_THREADS) {
-        const int qq = e / (D / 4), d = (e % (D / 4)) * 4;
-        float mw[AT_WAVES], M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < AT_WAVES; ++w) {
-            mw[w] = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS)[TILE_RT * WSTR + qq];
-            M = fmaxf(M, mw[w]);
-        }
-        f4 acc4 = f4{0.f, 0.f, 0.f, 0.f};
-        float lsum = 0.f;
-#pragma unroll
-        for (int w = 0; w < AT_WAVES; ++w) {
-            const float* pw = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS);
-            const float wgt = (mw[w] == -INFINITY) ? 0.f : exp2f(mw[w] - M);
-            const f4 ov = *reinterpret_cast<const f4*>(pw + qq * WSTR + d);
-            acc4[0] += wgt * ov[0]; acc4[1] += wgt * ov[1]; acc4[2] += wgt * ov[2]; acc4[3] += wgt * ov[3];
-            lsum += wgt * pw[TILE_RT * WSTR + 16 + qq];
-        }
-        *reinterpret_cast<f4*>(part_o + (pbase + qq) * D + d) = acc4;
-        if (d == 0) *reinterpret_cast<float2*>(part_ml + (pbase + qq) * 2) = make_float2(M, lsum);
-    }
+#include "kvz_decode_merge.inc"
 }
 
 // merge the partials of the key ranges.  grid = (Hkv, row tiles, 16 query rows); the body is combine_partials of kvz_combine.h.

@@ -100,23 +100,6 @@ __global__ __launch_bounds__(FP_THREADS) void fork_prefill_kernel(
 
     __shared__ __attribute__((aligned(16))) char lds[FP_WAVES * C::WAVE_LDS];
     char* wl = lds + wave * C::WAVE_LDS;
-    const float sl2 = scale * LOG2E;      // work in the exp2 domain
-
-    // stationary Q fragment (B operand of S^T = K.Q^T): col = query row, k = head-dim slice
-    v8 qf[C::KK];
-    {
-        const T* qp = q + (rvalid ? h * qs_head + g_l * qs_group + (int64_t)(cu0 + p_l) * qs_pos : 0) + quad * 8;
-#pragma unroll
-        for (int kk = 0; kk < C::KK; ++kk) {
-            u32x4 raw = *reinterpret_cast<const u32x4*>(qp + kk * 32);
-            if (!rvalid) raw = u32x4{0, 0, 0, 0};
-            qf[kk] = __builtin_bit_cast(v8, raw);
-        }
-    }
-    float m_run = -INFINITY, l_run = 0.f;
-    f4 o[C::DB];
-#pragma unroll
-    for (int db = 0; db < C::DB; ++db) o[db] = f4{0.f, 0.f, 0.f, 0.f};
 
     // rows past the wave's last key are clamped to it (always a row that exists) and masked below
     auto load_k = [&](u32x4 (&kr)[2][C::KK], int t0) {
@@ -139,74 +122,8 @@ __global__ __launch_bounds__(FP_THREADS) void fork_prefill_kernel(
             vr[it] = *reinterpret_cast<const u32x4*>(vp + (c % C::CPR) * 16);
         }
     };
-    auto compute_tile = [&](u32x4 (&kr)[2][C::KK], u32x4 (&vr)[C::VLOADS], int t0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int it = 0; it < C::VLOADS; ++it) {
-            const int c = it * WAVE + lane;
-            *reinterpret_cast<u32x4*>(wl + (c / C::CPR) * C::VSTRIDE + (c % C::CPR) * 16) = vr[it];
-        }
-        f4 s[2];
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-            s[sub] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < C::KK; ++kk) s[sub] = Half<T>::mfma(__builtin_bit_cast(v8, kr[sub][kk]), qf[kk], s[sub]);
-        }
-        float sv[8];
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int key = t0 + (j >> 2) * 16 + quad * 4 + (j & 3);
-            float x = s[j >> 2][j & 3] * sl2;
-            x = key < limit ? x : -INFINITY;                // the causal diagonal of THIS row, and the end of the keys
-            sv[j] = x;
-            tmax = fmaxf(tmax, x);
-        }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float m_new = fmaxf(m_run, tmax);
-        const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = exp2f(m_run - m_safe);
-        float psum = 0.f;
-        v8 pb;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float p = exp2f(sv[j] - m_safe);
-            psum += p;
-            pb[j] = (T)p;
-        }
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int db = 0; db < C::DB; ++db) {
-            o[db][0] *= alpha; o[db][1] *= alpha; o[db][2] *= alpha; o[db][3] *= alpha;
-        }
-        const char* trp = wl + (quad * 4 + (l15 >> 2)) * C::VSTRIDE + (l15 & 3) * 8;
-#pragma unroll
-        for (int db = 0; db < C::DB; ++db) {
-            s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(trp + db * 32));
-            s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(trp + 16 * C::VSTRIDE + db * 32));
-            s8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            o[db] = Half<T>::mfma(__builtin_bit_cast(v8, both), pb, o[db]);
-        }
-    };
-
-    // the wave's key tiles, the next one requested (unconditionally: clamped rows) before the current one is computed
-    u32x4 kraw[2][C::KK], vraw[C::VLOADS], knext[2][C::KK], vnext[C::VLOADS];
-    load_k(kraw, 0);
-    load_v(vraw, 0);
-#pragma unroll 1
-    for (int t0 = 0; t0 < kend; t0 += TILE_KT) {
-        load_k(knext, t0 + TILE_KT);
-        load_v(vnext, t0 + TILE_KT);
-        compute_tile(kraw, vraw, t0);
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int kk = 0; kk < C::KK; ++kk) kraw[sub][kk] = knext[sub][kk];
-#pragma unroll
-        for (int it = 0; it < C::VLOADS; ++it) vraw[it] = vnext[it];
-    }
+    const int k0 = 0;                                       // first key of the walk
+#include "kvz_prefill_walk.inc"
 
     // ---- epilogue: merge with the partial result over the shared segments, one division, one cast ----
     float lr = l_run;

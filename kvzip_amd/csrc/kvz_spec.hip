@@ -14,10 +14,11 @@
 //   spec_combine_kernel  per (head, position, group row): merges the partials of the head's key ranges and of the triangle.
 //                        Final normalisation: out = fp16/bf16(a / l)  (the 'div' form of tests/attn_probes.py, like the decode combine
 //                        of kvz_attn.hip).
-// The steps of the wave tile are spelled out as in every kernel on kvz_wave_tile.h, in kvz_spec_step.h: the work of a
-// block for one item is ONE function (spec_item) instantiated for the two kinds of item, so that the shared items keep compile-time
-// row strides and a scalar key limit.  The header and the body of a block (kvz_spec_block.inc) are shared with the tree form of the
-// step, kvz_tree.hip, whose attention kernel is a unit of its own so that the kernels here compile as they always did.
+// The work of a block for one item is ONE function (spec_item of kvz_spec_step.h) instantiated for the two kinds of item, so that the
+// shared items keep compile-time row strides and a scalar key limit; its tile step, key loop and merge are the text that
+// fork_attn_kernel includes too (kvz_nt_step.inc, kvz_nt_merge.inc: DESIGN.md 3.12).  The header and the body of a block
+// (kvz_spec_block.inc) are shared with the tree form of the step, kvz_tree.hip, whose attention kernel is a unit of
+// its own so that the kernels here compile as they always did.
 #include "kvz_spec_step.h"
 #include "../../include/kvzip_hip_spec.h"
 

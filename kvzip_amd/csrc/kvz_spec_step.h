@@ -91,142 +91,13 @@ __device__ __forceinline__ void spec_item(const T* __restrict__ q, const char* k
             vr[it] = *reinterpret_cast<const u32x4*>(vbase + (int64_t)key * vstr + (c % C::CPR) * 16);
         }
     };
-    // Two row tiles at head dim 128 leave no registers for a second K and V buffer (kvz_fork.hip: 51 registers spilled with them): there
-    // the next tile's V rows are requested into the SAME registers right after the current ones have gone to LDS, and its K rows right
-    // after the S^T products have consumed the current ones.
-    constexpr bool VLATE = NT * D > 128;
-    u32x4 kraw[2][C::KK], vraw[C::VLOADS], knext[VLATE ? 1 : 2][C::KK], vnext[VLATE ? 1 : C::VLOADS];
-    // one 32-key tile of this wave, applied to the NT row tiles
-    auto compute_tile = [&](u32x4 (&kr)[2][C::KK], u32x4 (&vr)[C::VLOADS], int t0, int t_next, auto refill) __attribute__((always_inline)) {
-#pragma unroll
-        for (int it = 0; it < C::VLOADS; ++it) {
-            const int c = it * WAVE + lane;
-            *reinterpret_cast<u32x4*>(wl + (c / C::CPR) * C::VSTRIDE + (c % C::CPR) * 16) = vr[it];
-        }
-        if constexpr (decltype(refill)::value) load_v(vr, t_next);
-        f4 s[NT][2];
-#pragma unroll
-        for (int i = 0; i < NT; ++i)
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub) {
-                s[i][sub] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int kk = 0; kk < C::KK; ++kk)
-                    s[i][sub] = Half<T>::mfma(__builtin_bit_cast(v8, kr[sub][kk]), qf[i][kk], s[i][sub]);
-            }
-        if constexpr (decltype(refill)::value) load_k(kr, t_next);  // (the K fragments are spent: the next tile's take their registers)
-        v8 pb[NT];
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            float sv[8];
-            float tmax = -INFINITY;
-            const int limit = TRI ? lim[i] : c1;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int key = t0 + (j >> 2) * 16 + quad * 4 + (j & 3);
-                float x = s[i][j >> 2][j & 3] * sl2;
-                if constexpr (TREE) x = ((vis[i] >> (key & 63)) & 1) ? x : -INFINITY;  // (key < c1 <= t <= 64; no bit at or above c1)
-                else x = key < limit ? x : -INFINITY;
-                sv[j] = x;
-                tmax = fmaxf(tmax, x);
-            }
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            const float m_new = fmaxf(m_run[i], tmax);
-            const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
-            const float alpha = exp2f(m_run[i] - m_safe);
-            float psum = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float p = exp2f(sv[j] - m_safe);
-                psum += p;
-                pb[i][j] = (T)p;
-            }
-            l_run[i] = l_run[i] * alpha + psum;
-            m_run[i] = m_new;
-#pragma unroll
-            for (int db = 0; db < C::DB; ++db) {
-                o[i][db][0] *= alpha; o[i][db][1] *= alpha; o[i][db][2] *= alpha; o[i][db][3] *= alpha;
-            }
-        }
-        const char* trp = wl + (quad * 4 + (l15 >> 2)) * C::VSTRIDE + (l15 & 3) * 8;
-#pragma unroll
-        for (int db = 0; db < C::DB; ++db) {
-            s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(trp + db * 32));
-            s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(trp + 16 * C::VSTRIDE + db * 32));
-            s8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-            for (int i = 0; i < NT; ++i) o[i][db] = Half<T>::mfma(__builtin_bit_cast(v8, both), pb[i], o[i][db]);
-        }
-    };
-    // The wave's tiles, one requested AHEAD of the one being computed; the steady-state loop issues the next tile's loads
-    // UNCONDITIONALLY and the last tile is computed after the loop (the load structure of varlen_attn_split2_kernel).
-    const int t_first = c0 + wave * TILE_KT;
-    constexpr int T_STEP = SP_WAVES * TILE_KT;
-    if (t_first < c1) {
-        load_k(kraw, t_first);
-        load_v(vraw, t_first);
-        int t0 = t_first;
-#pragma unroll 1
-        for (; t0 + T_STEP < c1; t0 += T_STEP) {
-            if constexpr (!VLATE) {
-                load_k(knext, t0 + T_STEP);
-                load_v(vnext, t0 + T_STEP);
-            }
-            compute_tile(kraw, vraw, t0, t0 + T_STEP, std::integral_constant<bool, VLATE>{});
-            if constexpr (!VLATE) {
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                    for (int kk = 0; kk < C::KK; ++kk) kraw[sub][kk] = knext[sub][kk];
-#pragma unroll
-                for (int it = 0; it < C::VLOADS; ++it) vraw[it] = vnext[it];
-            }
-        }
-        compute_tile(kraw, vraw, t0, 0, std::false_type{});
-    }
+// (key < c1 <= t <= 64 in a triangle item of the tree form, and no bit of vis[] at or above c1)
+#define KVZ_NT_VISIBLE(i, key) (TREE ? (bool)((vis[i] >> ((key) & 63)) & 1) : (key) < (TRI ? lim[i] : c1))
+    constexpr int BLOCK_WAVES = SP_WAVES;
+#include "kvz_nt_step.inc"
 
-    // ---- merge the 8 waves of the block through LDS, one row tile after the other (each wave stages in its own V tile) ----
-    constexpr int WSTR = D + 4;                          // floats per staged row (bank-conflict-free, see kvz_attn.hip)
-    static_assert((TILE_RT * WSTR + 2 * TILE_RT) * 4 <= C::WAVE_LDS, "the wave's V tile holds its merge staging");
-    float* wo = reinterpret_cast<float*>(wl);            // [16 q][D + 4]
-    float* wm = wo + TILE_RT * WSTR;                     // [16] m, [16] l
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        float lr = l_run[i];
-        lr += __shfl_xor(lr, 16, 64);
-        lr += __shfl_xor(lr, 32, 64);
-        const int rv = rows_valid[i];
-        if (l15 < rv) {
-#pragma unroll
-            for (int db = 0; db < C::DB; ++db) *reinterpret_cast<f4*>(wo + l15 * WSTR + db * 16 + quad * 4) = o[i][db];
-            if (quad == 0) { wm[l15] = m_run[i]; wm[16 + l15] = lr; }
-        }
-        __syncthreads();
-        const int64_t pbase = slot0 + (int64_t)i * TILE_RT;
-        for (int e = threadIdx.x; e < rv * (D / 4); e += SP_THREADS) {
-            const int qq = e / (D / 4), d = (e % (D / 4)) * 4;
-            float mw[SP_WAVES], M = -INFINITY;
-#pragma unroll
-            for (int w = 0; w < SP_WAVES; ++w) {
-                mw[w] = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS)[TILE_RT * WSTR + qq];
-                M = fmaxf(M, mw[w]);
-            }
-            f4 acc4 = f4{0.f, 0.f, 0.f, 0.f};
-            float lsum = 0.f;
-#pragma unroll
-            for (int w = 0; w < SP_WAVES; ++w) {
-                const float* pw = reinterpret_cast<const float*>(lds + w * C::WAVE_LDS);
-                const float wgt = (mw[w] == -INFINITY) ? 0.f : exp2f(mw[w] - M);
-                const f4 ov = *reinterpret_cast<const f4*>(pw + qq * WSTR + d);
-                acc4[0] += wgt * ov[0]; acc4[1] += wgt * ov[1]; acc4[2] += wgt * ov[2]; acc4[3] += wgt * ov[3];
-                lsum += wgt * pw[TILE_RT * WSTR + 16 + qq];
-            }
-            *reinterpret_cast<f4*>(po + (pbase + qq) * D + d) = acc4;
-            if (d == 0) *reinterpret_cast<float2*>(pml + (pbase + qq) * 2) = make_float2(M, lsum);
-        }
-        __syncthreads();  // (the staging of this row tile has been read: the next one may overwrite it)
-    }
+    constexpr int rt_first = 0;  // (slot0 is the slot of row tile rt0)
+#include "kvz_nt_merge.inc"
 }
 
 // work items of the shared part: the decode kernel's count (one block per CU) less the triangle items of the same launch, never below

@@ -6,10 +6,16 @@
 //                 no LDS) and the stationary Q fragment as the B operand: lane & 15 = one query row, lane >> 4 = a slice of the keys;
 //   softmax       online, fp32, in the exp2 domain, state in registers;
 //   O^T += V^T.P^T with the V rows staged through a padded per-wave LDS tile (VSTRIDE) and read back transposed by ds_read_b64_tr_b16.
-// The steps of the tile themselves (Q fragment, clamped K and V loads, V staging, products, softmax update, read-back, the merge of a
-// block's waves) are spelled out in every kernel: as calls into shared functions each of them - even the V staging alone, even with
-// the lane handed in - moved the compiler's schedule of the key loop of the decode kernel.  The combine of the
-// partials, a launch of its own, is shared: kvz_combine.h.
+// The steps of the tile themselves exist once per family of kernels, as TEXT that the kernels include:
+//   one row tile per block, 8 waves over the keys (kvz_attn.hip, kvz_retain.hip, kvz_multi.hip)   kvz_decode_state.inc (Q fragment, state),
+//                                                       kvz_decode_step.inc (tile step), kvz_decode_loop.inc (key loop), kvz_decode_merge.inc
+//   one wave per row tile (kvz_fork_prefill.hip, kvz_multi_prefill.hip)                           kvz_prefill_walk.inc
+//   NT row tiles per block (kvz_fork.hip, kvz_spec_step.h for kvz_spec.hip and kvz_tree.hip)      kvz_nt_step.inc, kvz_nt_merge.inc
+// A kernel holds what is its own - work-item lookup, addresses and clamped loads, the append, the mask, where partials go - as the
+// locals and lambdas a fragment's leading comment asks for.  Text, not functions: as calls into shared function templates each step -
+// even the V staging alone, even with the lane handed in - moved the compiler's schedule of the key loop of the decode kernel, while
+// included text leaves the device code of every kernel as it was (tools/device_code_diff.py).  A new kernel on this tile includes
+// the fragments; a fix to a step is made once.  The combine of the partials, a launch of its own, is shared as a function: kvz_combine.h.
 #pragma once
 #include "kvz_common.h"
 
